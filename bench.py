@@ -7,7 +7,12 @@ into contiguous shards (strong scaling: 512 per GPU on 8 GPUs), with weak scalin
 GPU) measured as a secondary row; the device-format bootstrapping key is produced once on
 rank 0 and broadcast over RCCL (xGMI); there is no collective in the data path.
 
-Usage: python bench.py [--gpus N --steps K --warmup W]
+A plain run sets up, warms up, times the steps and prints the result line.  --full adds everything
+else the benchmark measures or checks: the decrypt and bit-exact checks of the timed outputs, the
+CPU baseline, the keyswitch / B = 512 / weak-scaling / PCIe-inclusive / SDFG-route rows and the
+gather check.  --dump-outputs DIR writes a fixed sample of the last timed step's output rows.
+
+Usage: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
        (N>1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
 """
 from __future__ import annotations
@@ -224,8 +229,42 @@ def parse():
     ap.add_argument("--check-gather", action="store_true",
                     help="rank 0 checks the whole gathered batch: every row decrypts to its rank's LUT[m], and "
                          "two rows per rank are bit-exact vs the oracle (inputs regenerated from the seeds)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the decrypt / bit-exact checks, the CPU "
+                         "baseline, the keyswitch, B = 512, weak-scaling, PCIe-inclusive and SDFG-route rows and "
+                         "--check-gather (the --no-* / --verify / --cpu-* options select among them); a plain "
+                         "run only sets up, warms up, times the steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the output rows of the last timed step (a fixed, seeded "
+                         "sample of rows when the batch is large) as float64 DIR/<name>.npy: the high and low "
+                         "32 bits of every u64 word, exact, and the sampled row numbers")
     return ap.parse_args()
 
+
+# --dump-outputs: at most this many bytes per run (both halves of every word, every rank)
+DUMP_BUDGET_BYTES = 48 << 20
+DUMP_MAX_ROWS = 1024
+
+
+def dump_rows(batch: int, row_words: int, world: int = 1) -> np.ndarray:
+    """The rows of a rank's output that --dump-outputs writes: all of them when they fit the budget,
+    else a sorted sample drawn with a fixed seed (the same rows in every run and every build)."""
+    per_row = 2 * 8 * row_words  # two float64 halves per u64 word
+    count = max(1, min(batch, DUMP_MAX_ROWS // world, DUMP_BUDGET_BYTES // world // per_row))
+    if count >= batch:
+        return np.arange(batch, dtype=np.int64)
+    return np.sort(np.random.RandomState(20240).choice(batch, size=count, replace=False)).astype(np.int64)
+
+
+def dump_outputs(path: str, rows_u64: np.ndarray, rows: np.ndarray, rank: int = 0, world: int = 1) -> None:
+    """Write the sampled output rows as float64 arrays a reader without u64 support can compare exactly:
+    <name>_hi32 / <name>_lo32 hold the high / low 32 bits of every word, <name>_rows the row numbers."""
+    os.makedirs(path, exist_ok=True)
+    name = "pbs_out" if world == 1 else f"pbs_out_rank{rank}"
+    words = np.ascontiguousarray(rows_u64).view(np.uint64)
+    np.save(os.path.join(path, name + "_hi32.npy"), (words >> np.uint64(32)).astype(np.float64))
+    np.save(os.path.join(path, name + "_lo32.npy"), (words & np.uint64(0xFFFFFFFF)).astype(np.float64))
+    np.save(os.path.join(path, name + "_rows.npy"), rows.astype(np.float64))
 
 
 
@@ -356,9 +395,14 @@ def main():
     else:
         global_batch = args.batch
 
+    # ---- what the timed path computed in its last step, before anything else touches the device
+    if args.dump_outputs:
+        picked = dump_rows(args.batch, p.lwe_out_size, world)
+        dump_outputs(args.dump_outputs, B.to_host(d_out)[picked], picked, rank, world)
+
     # ---- weak scaling (cfg2, N > 1): every rank its own full batch of 4096, same timing rule
     weak_res = None
-    if strong and world > 1 and args.config == "cfg2" and not args.weak:
+    if args.full and strong and world > 1 and args.config == "cfg2" and not args.weak:
         _, _, cts_w = shard_inputs(rank, 4096)
         d_in_w = B.to_device(cts_w, dev)
         d_out_w = torch.empty((4096, p.lwe_out_size), dtype=torch.int64, device=dev)
@@ -385,7 +429,7 @@ def main():
     #      of 8 GPUs runs in the strong-scaling 8-GPU job (the six-wave kernel's batch);
     #      timed the same way on this GPU, its 8x is a projection, not an 8-GPU measurement
     share_res = None
-    if world == 1 and args.config == "cfg2" and strong and args.global_batch == 4096 and not args.no_share:
+    if args.full and world == 1 and args.config == "cfg2" and strong and args.global_batch == 4096 and not args.no_share:
         nb_s = 512
         d_out_s = torch.empty((nb_s, p.lwe_out_size), dtype=torch.int64, device=dev)
         d_in_s = d_in[:nb_s]
@@ -413,7 +457,7 @@ def main():
 
     # ---- secondary row: batched keyswitch kN -> n of this batch, after the PBS
     ks_res = None
-    if not args.no_ks:
+    if args.full and not args.no_ks:
         ksk = B.ksk_generate(p, glwe_sk, lwe_sk, 6)
         # allocated the runtime's way (cuda_malloc_async, context.h:134-139): the int8 key bytes of
         # the matrix-core path are then built once and reused across calls
@@ -467,7 +511,7 @@ def main():
     # ---- end-to-end including PCIe: host inputs -> H2D -> PBS -> D2H -> host outputs (DESIGN.md §6;
     # never `value`, which is the device-resident rate)
     e2e = None
-    if not args.no_e2e:
+    if args.full and not args.no_e2e:
         h_in = torch.from_numpy(cts.view(np.int64)).pin_memory()
         h_out = torch.empty((args.batch, p.lwe_out_size), dtype=torch.int64).pin_memory()
         torch.cuda.synchronize()
@@ -483,7 +527,7 @@ def main():
     # stream_emulator_*): a KS -> PBS table lookup on host memrefs, timed end to end per run (put
     # the batch, get the outputs: H2D, keyswitch, bootstrap, D2H, intermediates resident in HBM)
     sdfg_res = None
-    if world == 1 and args.config == "cfg2" and not args.no_ks and not args.no_sdfg:
+    if args.full and world == 1 and args.config == "cfg2" and not args.no_ks and not args.no_sdfg:
         from concrete_amd import runtime as R
         width_s = 2  # KS -> PBS chains keep p <= 2 at the cfg2 keyswitch noise
         table_s = np.array([3, 0, 2, 1], dtype=np.uint64)
@@ -570,19 +614,22 @@ def main():
         full = D.gather_rows(d_out, global_batch, dst=0)
         torch.cuda.synchronize()
         t_gather = time.perf_counter() - t0
-        if rank == 0 and args.check_gather:
+        if rank == 0 and args.full and args.check_gather:
             gather_check = check_gather(B.to_host(full), world, global_batch)
         del full
 
-    # ---- correctness of what was timed: decrypt-level on every row, bit-exact sample (rank 0)
-    out = B.to_host(d_out)
-    dec = B.lwe_decrypt(glwe_sk, out, p.big_n)
-    ok = sum(int(B.decode(d, width) == table[m]) for d, m in zip(dec, msgs))
-    ok_all = ok
-    if world > 1:
-        t = torch.tensor([ok], dtype=torch.int64, device=dev)
-        dist.all_reduce(t)
-        ok_all = int(t.item())
+    # ---- correctness of what was timed (--full): decrypt-level on every row, bit-exact sample (rank 0)
+    ok_all = None
+    if args.full:
+        out = B.to_host(d_out)
+        dec = B.lwe_decrypt(glwe_sk, out, p.big_n)
+        ok = sum(int(B.decode(d, width) == table[m]) for d, m in zip(dec, msgs))
+        ok_all = ok
+        if world > 1:
+            t = torch.tensor([ok], dtype=torch.int64, device=dev)
+            dist.all_reduce(t)
+            ok_all = int(t.item())
+    verify = args.verify if args.full else 0
     cpu_threads = args.cpu_threads or host_cpus()["usable"]
 
     result = None
@@ -607,8 +654,8 @@ def main():
             "frac": round(traffic / kern_s / 1e9 / HBM_PEAK_GBS, 4),
             "note": "measured DRAM bytes (roofline.traffic) per launch / kernel time"}
         # the CPU baseline is timed at N = 1 only (a reported baseline, not part of the scaling runs)
-        cpu_leg = not args.no_cpu_baseline and world == 1
-        if args.verify or cpu_leg:
+        cpu_leg = args.full and not args.no_cpu_baseline and world == 1
+        if verify or cpu_leg:
             from oracle import pyoracle as O  # checker / CPU baseline only
             opt = args.config.startswith("opt")
             if bsk is None:
@@ -623,9 +670,9 @@ def main():
                 op = O.Params(n=p.n, k=p.k, N=p.N, l=p.level, logB=p.base_log, limbs=O.limbs_for(p.N))
                 kw = {"fbsk": O.bsk_to_fourier(op, bsk)}
                 desc = f"exact-limb f64 FFT restatement, {op.limbs} limbs"
-            if args.verify:
-                ref, _ = O.pbs_batch(op, cts[: args.verify], acc[None, :], nthreads=cpu_threads, **kw)
-                bitexact = bool(np.array_equal(ref, out[: args.verify]))
+            if verify:
+                ref, _ = O.pbs_batch(op, cts[:verify], acc[None, :], nthreads=cpu_threads, **kw)
+                bitexact = bool(np.array_equal(ref, out[:verify]))
             if cpu_leg:
                 sample = cts[: args.cpu_sample]
                 # the reference's own arithmetic for every config (concrete-cpu's fft64: one f64
@@ -673,8 +720,10 @@ def main():
             "secondary": {"keyswitch": ks_res, "sdfg_route": sdfg_res, "weak_scaling": weak_res,
                           "whole_node_share_b512": share_res,
                           "pcie_inclusive_pbs_per_s": None if e2e is None else round(e2e * world, 1)},
-            "checks": {"decrypt_ok": f"{ok_all}/{global_batch}", "bitexact_rows": args.verify, "gather": gather_check,
-                       "bitexact": bitexact},
+            "checks": {"decrypt_ok": None if ok_all is None else f"{ok_all}/{global_batch}", "bitexact_rows": verify,
+                       "gather": gather_check, "bitexact": bitexact},
+            "full": args.full,
+            "dumped_outputs": args.dump_outputs,
         }
         print(json.dumps(result), flush=True)
     if world > 1:

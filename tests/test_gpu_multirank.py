@@ -26,7 +26,7 @@ def test_bench_two_ranks():
     env = dict(os.environ, CONCRETE_HIP_DIST_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-ks", "--verify", "4"]
+           "--gpus", "2", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-ks", "--verify", "4"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -48,8 +48,8 @@ def test_bench_eight_ranks_configs2_shape():
     env = dict(os.environ, CONCRETE_HIP_DIST_BACKEND="gloo", OMP_NUM_THREADS="2")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", "8", "--steps", "1", "--warmup", "0", "--weak", "--batch", "8192", "--no-cpu-baseline", "--no-ks",
-           "--verify", "2", "--check-gather"]
+           "--gpus", "8", "--steps", "1", "--warmup", "0", "--weak", "--batch", "8192", "--full", "--no-cpu-baseline",
+           "--no-ks", "--verify", "2", "--check-gather"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -59,6 +59,43 @@ def test_bench_eight_ranks_configs2_shape():
     assert d["checks"]["decrypt_ok"] == "65536/65536"
     g = d["checks"]["gather"]
     assert g["rows"] == 65536 and g["decrypt_ok"] == "65536/65536" and g["bitexact"] is True
+
+
+def test_plain_run_is_lean_and_dumps_last_step(tmp_path):
+    """A plain run (no --full) at a small batch: the line carries the headline fields and none of the
+    --full rows, and the dumped rows are the PBS outputs of the seeded inputs (every one decrypts to
+    its message's table entry)."""
+    # torch before the library, as in every GPU test: torch brings its own copy of the HIP runtime, and
+    # a process that loads libconcrete_hip.so first ends up with two runtimes mapped
+    import torch  # noqa: F401
+    import numpy as np
+
+    import bench
+    from concrete_amd import backend as B
+    from test_bench_cli import dumped_words
+    out_dir = str(tmp_path / "dump")
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--global-batch", "96", "--dump-outputs", out_dir]
+    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["full"] is False
+    assert d["unit"] == "PBS/s" and d["higher_is_better"] is True and d["dtype"] == "u64"
+    assert d["ms_per_step"] > 0 and abs(d["value"] - 96 / (d["ms_per_step"] * 1e-3)) <= 0.01 * d["value"]
+    assert d["cpu_baseline"] is None and all(v is None for v in d["secondary"].values())
+    assert d["checks"] == {"decrypt_ok": None, "bitexact_rows": 0, "gather": None, "bitexact": None}
+
+    p, width = B.CFG2, 3
+    got = dumped_words(out_dir)
+    rows = np.load(os.path.join(out_dir, "pbs_out_rows.npy")).astype(np.int64)
+    assert got.shape == (96, p.lwe_out_size) and np.array_equal(rows, bench.dump_rows(96, p.lwe_out_size))
+    rng = np.random.RandomState(1000)  # bench.py's shard_inputs(rank 0)
+    table = rng.randint(0, 1 << width, size=1 << width)
+    msgs = rng.randint(0, 1 << width, size=96)
+    dec = B.lwe_decrypt(B.binary_key(p.big_n, 2), got, p.big_n)
+    assert [B.decode(x, width) for x in dec] == [int(table[m]) for m in msgs[rows]]
 
 
 RCCL_SCRIPT = r'''

@@ -6,6 +6,8 @@ TAG=${1:-pmc}
 PASSES=${2:-abcde}
 shift 2 || true
 EXTRA="$*"   # extra bench.py arguments (e.g. --config cfg4)
+# --full below: the passes also cover the keyswitch and SDFG-route kernels, which a plain run leaves out
+BENCH=$(cd "$(dirname "$0")/.." && pwd)/bench.py
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp
@@ -13,7 +15,7 @@ export TMPDIR=/tmp PYTHONUNBUFFERED=1 CONCRETE_BENCH_PROGRESS=1
 run() {  # name counters...
   local name=$1; shift
   timeout -k 10 ${PMC_TIMEOUT:-240} rocprofv3 --pmc "$@" --output-format csv -d $OUT/$name -o run -- \
-    python $GRAFT_REPO_ROOT/bench.py --steps 1 --warmup 0 --no-cpu-baseline --verify 0 --no-e2e --no-share $EXTRA > $OUT/$name.log 2>&1
+    python $BENCH --full --steps 1 --warmup 0 --no-cpu-baseline --verify 0 --no-e2e --no-share $EXTRA > $OUT/$name.log 2>&1
 }
 # HBM traffic passes first (a later pass that fails or hangs leaves them in place)
 [[ $PASSES == *d* ]] && run d FETCH_SIZE

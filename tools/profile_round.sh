@@ -9,7 +9,7 @@ mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 for C in cfg2 cfg4; do
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$C -o run -- \
-    python3 $R/bench.py --config $C --steps 5 --warmup 2 --no-cpu-baseline --verify 0 --no-ks > $O/trace_$C.log 2>&1
+    python3 $R/bench.py --full --config $C --steps 5 --warmup 2 --no-cpu-baseline --verify 0 --no-ks > $O/trace_$C.log 2>&1
 done
 cd $R
 bash tools/pmc.sh $TAG/pmc_cfg2 de
