@@ -37,6 +37,14 @@ SIGNATURES = {
     "cuda_add_lwe_ciphertext_vector_plaintext_vector_64": (None, [vp, u32, vp, vp, vp, u32, u32]),
     "cuda_mult_lwe_ciphertext_vector_cleartext_vector_64": (None, [vp, u32, vp, vp, vp, u32, u32]),
     "cuda_negate_lwe_ciphertext_vector_64": (None, [vp, u32, vp, vp, u32, u32]),
+    "scratch_cuda_extract_bits_64": (None, [vp, u32, C.POINTER(vp), u32, u32, u32, u32, u32, u32, C.c_bool]),
+    "cuda_extract_bits_64": (None, [vp, u32, vp, vp, vp, vp, vp, u32, u32, u32, u32, u32, u32, u32, u32, u32, u32, u32,
+                                    u32]),
+    "cleanup_cuda_extract_bits": (None, [vp, u32, C.POINTER(vp)]),
+    "concrete_hip_extract_bits": (i32, [vp, u32, vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, u32, u32, u32, u32,
+                                        u32, vp, u64]),
+    "concrete_hip_extract_bits_scratch_bytes": (u64, [u32, u32, u32, u32, u32, u32]),
+    "concrete_hip_extract_bits_supported": (i32, [u32, u32, u32, u32, u32, u32, u32, u32]),
     "concrete_hip_abi_version": (u32, []),
     "concrete_hip_last_error": (C.c_char_p, []),
     "concrete_hip_pbs_supported": (i32, [u32, u32, u32, u32]),

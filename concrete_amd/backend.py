@@ -300,3 +300,87 @@ def keyswitch(p: PbsParams, ksk_dev, lwe_in, out=None, in_idx=None, out_idx=None
         _stream(device), _gpu_index(device), _ptr(out), _ptr(out_idx), _ptr(lwe_in), _ptr(in_idx), _ptr(ksk_dev),
         p.big_n, p.n, p.ks_base_log, p.ks_level, B), "concrete_hip_keyswitch")
     return out
+
+
+# ---------------------------------------------------------------------------------------
+# WoP-PBS stage 1: bit extraction (concrete_hip_extract_bits)
+# ---------------------------------------------------------------------------------------
+def extract_bits_supported(p: PbsParams) -> bool:
+    return bool(_native.lib().concrete_hip_extract_bits_supported(p.big_n, p.n, p.k, p.N, p.base_log, p.level,
+                                                                 p.ks_base_log, p.ks_level))
+
+
+def extract_bits_scratch_bytes(p: PbsParams, num_samples: int, max_number_of_bits: int) -> int:
+    return int(_native.lib().concrete_hip_extract_bits_scratch_bytes(p.big_n, p.n, p.k, p.N, num_samples,
+                                                                     max_number_of_bits))
+
+
+def _per_row(x, rows: int, what: str) -> np.ndarray:
+    a = np.full(rows, x, dtype=np.uint32) if np.isscalar(x) else np.ascontiguousarray(x, dtype=np.uint32)
+    if a.shape != (rows,):
+        raise ValueError(f"{what}: {a.shape[0] if a.ndim == 1 else a.shape} entries for {rows} rows")
+    return a
+
+
+def extract_bits(p: PbsParams, fbsk, ksk_dev, lwe_in, number_of_bits, delta_log, out=None, out_row_offsets=None,
+                 scratch=None):
+    """Bit extraction on device tensors: lwe_in (B, kN+1) -> (sum nb, n+1) int64, per row the nb bits
+    starting at bit dl, most significant first, each encrypted times 2^63 under the small key.
+    number_of_bits / delta_log: ints or per-row sequences.  out_row_offsets: first output row of each
+    input row's block (default: packed in input order).  lwe_in is not modified."""
+    torch = _torch()
+    device = lwe_in.device
+    rows = lwe_in.shape[0]
+    nb = _per_row(number_of_bits, rows, "number_of_bits")
+    dl = _per_row(delta_log, rows, "delta_log")
+    offs = None if out_row_offsets is None else np.ascontiguousarray(out_row_offsets, dtype=np.uint64)
+    if offs is not None and offs.shape != (rows,):
+        raise ValueError(f"out_row_offsets: {offs.shape} for {rows} rows")
+    total = int(nb.astype(np.int64).sum())
+    if out is None:
+        out = torch.empty((total, p.n + 1), dtype=torch.int64, device=device)
+    elif out.shape[0] < total or out.shape[1] != p.n + 1 or not out.is_contiguous():
+        raise ValueError(f"out: need a contiguous (>= {total}, {p.n + 1}) tensor, got {tuple(out.shape)}")
+    _native.check(_native.lib().concrete_hip_extract_bits(
+        _stream(device), _gpu_index(device), _ptr(out), _ptr(lwe_in), _ptr(fbsk), _ptr(ksk_dev), _ptr(nb), _ptr(dl),
+        _ptr(offs), p.big_n, p.n, p.k, p.N, p.base_log, p.level, p.ks_base_log, p.ks_level, rows,
+        _ptr(scratch), 0 if scratch is None else scratch.numel() * scratch.element_size()),
+        "concrete_hip_extract_bits")
+    return out
+
+
+def crt_encode(v: int, modulus: int) -> int:
+    """CRT block encoding, compiler lib/Common/CRT.cpp:80-88: floor((v mod m) 2^64 / m)."""
+    return ((int(v) % int(modulus)) << 64) // int(modulus)
+
+
+def crt_bits(modulus: int) -> int:
+    """Bits extracted from a block of this modulus: ceil(log2 m) (wrappers.cpp:908-909)."""
+    return (int(modulus) - 1).bit_length()
+
+
+def crt_extract_bits(p: PbsParams, fbsk, ksk_dev, blocks, moduli):
+    """The bit-extraction front end of the runtime's CRT WoP-PBS (compiler lib/Runtime/wrappers.cpp:903-965)
+    for a batch: blocks (batch, len(moduli), kN+1) -> (batch, sum nb_i, n+1), per value the reference's order
+    [bits of block n-1 | ... | bits of block 0], each most significant bit first.  Block i yields
+    nb_i = ceil(log2 m_i) bits at delta_log 64 - nb_i, after 2^(63-nb_i) - 2^(59-nb_i) is taken off its body."""
+    torch = _torch()
+    device = blocks.device
+    batch, nblk = blocks.shape[0], blocks.shape[1]
+    assert nblk == len(moduli) and blocks.shape[2] == p.big_n + 1
+    nbs = [crt_bits(m) for m in moduli]
+    assert min(nbs) >= 1, "a CRT modulus must be at least 2"
+    per_value = sum(nbs)
+    flat = blocks.reshape(batch * nblk, p.big_n + 1)
+    sub = np.array([(-((1 << (63 - nb)) - ((1 << (59 - nb)) if nb <= 59 else 0))) % (1 << 64) for nb in nbs],
+                   dtype=np.uint64)
+    shifted = torch.empty_like(flat)
+    _native.lib().cuda_add_lwe_ciphertext_vector_plaintext_vector_64(
+        _stream(device), _gpu_index(device), _ptr(shifted), _ptr(flat), _ptr(to_device(np.tile(sub, batch), device)),
+        p.big_n, batch * nblk)
+    # block i of a value lands after the blocks above it
+    first = np.concatenate([np.cumsum(nbs[::-1])[::-1][1:], [0]]).astype(np.uint64)
+    offs = (np.arange(batch, dtype=np.uint64)[:, None] * np.uint64(per_value) + first[None, :]).reshape(-1)
+    out = extract_bits(p, fbsk, ksk_dev, shifted, np.tile(nbs, batch), np.tile([64 - nb for nb in nbs], batch),
+                       out_row_offsets=offs)
+    return out.reshape(batch, per_value, p.n + 1)

@@ -348,6 +348,52 @@ const void* generic_companion_key(const void* primary, uint32_t n, uint32_t k, u
   return d;
 }
 
+// What concrete_hip_pbs decides before it launches (shared with extract_bits.hip): the parameter
+// gate, the per-key exactness gate, and the key a launch reads — the caller's, or its general-format
+// companion for wide digits.  0, or the refusal's code with the message set; makes `gpu_index` current.
+int pbs_resolve_key(void* stream, uint32_t gpu_index, const void* fourier_bsk, uint32_t lwe_dimension,
+                    uint32_t glwe_dimension, uint32_t polynomial_size, uint32_t base_log, uint32_t level_count,
+                    PbsKey* out) {
+  bool generic = !pbs_params_ok(glwe_dimension, polynomial_size, level_count, base_log);
+  if (generic && !pbs_needs_generic_key(glwe_dimension, polynomial_size, level_count, base_log)) {
+    set_error("pbs: unsupported parameters k=%u N=%u level=%u base_log=%u", glwe_dimension, polynomial_size,
+              level_count, base_log);
+    return -2;
+  }
+  set_device(gpu_index);
+  const void* key = fourier_bsk;
+  uint32_t limbs = default_limbs(glwe_dimension, polynomial_size, level_count);
+  const KeyKind kind = key_format(glwe_dimension, polynomial_size, level_count).kind;
+  if (!generic && key_bound_check(fourier_bsk, kind, glwe_dimension, polynomial_size, level_count, base_log) != 0) {
+    // this key's spectrum is too large for the hand-tuned kernel at this base_log: the general path's
+    // narrower limbs may still be exact (its companion's own bound is checked below)
+    if (kind == KeyKind::GENERIC ||
+        !generic_pbs_ok(glwe_dimension, polynomial_size, level_count, base_log) ||
+        !generic_companion_key(fourier_bsk, lwe_dimension, glwe_dimension, level_count, polynomial_size,
+                               (hipStream_t)stream))
+      return -2;  // message set by key_bound_check
+    generic = true;
+  }
+  if (generic) {
+    // digits wider than the hand-tuned kernel takes: the general path, on this key's companion
+    key = generic_companion_key(fourier_bsk, lwe_dimension, glwe_dimension, level_count, polynomial_size,
+                                (hipStream_t)stream);
+    if (!key) {
+      set_error("pbs: k=%u N=%u level=%u base_log=%u runs on the general path, whose key format this key is not "
+                "in and cannot be derived from (convert it through a keyset or "
+                "cuda_convert_lwe_programmable_bootstrap_key_64, or use concrete_hip_convert_bsk_generic + "
+                "concrete_hip_pbs_generic)",
+                glwe_dimension, polynomial_size, level_count, base_log);
+      return -2;
+    }
+    limbs = generic_key_format(glwe_dimension, polynomial_size, level_count).limbs;
+    if (key_bound_check(key, KeyKind::GENERIC, glwe_dimension, polynomial_size, level_count, base_log) != 0)
+      return -2;
+  }
+  out->key = key, out->limbs = limbs, out->generic = generic;
+  return 0;
+}
+
 }  // namespace chip
 
 using namespace chip;
@@ -574,42 +620,13 @@ int concrete_hip_pbs(void* stream, uint32_t gpu_index, uint64_t* lwe_array_out, 
     set_error("pbs: lwe_dimension must be > 0");
     return -3;
   }
-  bool generic = !pbs_params_ok(glwe_dimension, polynomial_size, level_count, base_log);
-  if (generic && !pbs_needs_generic_key(glwe_dimension, polynomial_size, level_count, base_log)) {
-    set_error("pbs: unsupported parameters k=%u N=%u level=%u base_log=%u", glwe_dimension, polynomial_size,
-              level_count, base_log);
-    return -2;
-  }
-  set_device(gpu_index);
-  const void* key = fourier_bsk;
-  uint32_t limbs = default_limbs(glwe_dimension, polynomial_size, level_count);
-  const KeyKind kind = key_format(glwe_dimension, polynomial_size, level_count).kind;
-  if (!generic && key_bound_check(fourier_bsk, kind, glwe_dimension, polynomial_size, level_count, base_log) != 0) {
-    // this key's spectrum is too large for the hand-tuned kernel at this base_log: the general path's
-    // narrower limbs may still be exact (its companion's own bound is checked below)
-    if (kind == KeyKind::GENERIC ||
-        !generic_pbs_ok(glwe_dimension, polynomial_size, level_count, base_log) ||
-        !generic_companion_key(fourier_bsk, lwe_dimension, glwe_dimension, level_count, polynomial_size,
-                               (hipStream_t)stream))
-      return -2;  // message set by key_bound_check
-    generic = true;
-  }
-  if (generic) {
-    // digits wider than the hand-tuned kernel takes: the general path, on this key's companion
-    key = generic_companion_key(fourier_bsk, lwe_dimension, glwe_dimension, level_count, polynomial_size,
-                                (hipStream_t)stream);
-    if (!key) {
-      set_error("pbs: k=%u N=%u level=%u base_log=%u runs on the general path, whose key format this key is not "
-                "in and cannot be derived from (convert it through a keyset or "
-                "cuda_convert_lwe_programmable_bootstrap_key_64, or use concrete_hip_convert_bsk_generic + "
-                "concrete_hip_pbs_generic)",
-                glwe_dimension, polynomial_size, level_count, base_log);
-      return -2;
-    }
-    limbs = generic_key_format(glwe_dimension, polynomial_size, level_count).limbs;
-    if (key_bound_check(key, KeyKind::GENERIC, glwe_dimension, polynomial_size, level_count, base_log) != 0)
-      return -2;
-  }
+  PbsKey pk;
+  if (const int rc = pbs_resolve_key(stream, gpu_index, fourier_bsk, lwe_dimension, glwe_dimension, polynomial_size,
+                                     base_log, level_count, &pk))
+    return rc;
+  const void* key = pk.key;
+  const uint32_t limbs = pk.limbs;
+  const bool generic = pk.generic;
   PbsArgs a{(hipStream_t)stream,
             lwe_array_out,
             lwe_output_indexes,
@@ -833,6 +850,97 @@ void cuda_keyswitch_lwe_ciphertext_vector_64(void* stream, uint32_t gpu_index, v
                              (const uint64_t*)ksk, lwe_dimension_in, lwe_dimension_out, base_log, level_count,
                              num_samples) != 0)
     die("cuda_keyswitch_lwe_ciphertext_vector_64");
+}
+
+// ----------------------------------------------------------------------------------------
+// bit extraction (WoP-PBS stage 1), reference names (concrete-cuda cuda_bind.rs:494-567)
+// ----------------------------------------------------------------------------------------
+// sizes of the buffers handed out by scratch_cuda_extract_bits_64 (the call itself carries none)
+static std::mutex g_eb_mu;
+static std::unordered_map<const void*, uint64_t> g_eb_scratch;
+
+void scratch_cuda_extract_bits_64(void* stream, uint32_t gpu_index, int8_t** bit_extract_buffer,
+                                  uint32_t glwe_dimension, uint32_t lwe_dimension, uint32_t polynomial_size,
+                                  uint32_t level_count, uint32_t number_of_inputs, uint32_t max_shared_memory,
+                                  bool allocate_gpu_memory) {
+  (void)max_shared_memory;
+  if (!bit_extract_buffer) {
+    set_error("null buffer pointer");
+    die("scratch_cuda_extract_bits_64");
+  }
+  if (key_format(glwe_dimension, polynomial_size, level_count).kind == KeyKind::NONE) {
+    set_error("scratch: unsupported parameters k=%u N=%u level=%u", glwe_dimension, polynomial_size, level_count);
+    die("scratch_cuda_extract_bits_64");
+  }
+  *bit_extract_buffer = nullptr;
+  // the call that follows names its number_of_bits only later: sized for the most (63)
+  const uint64_t bytes = concrete_hip_extract_bits_scratch_bytes(glwe_dimension * polynomial_size, lwe_dimension,
+                                                                 glwe_dimension, polynomial_size, number_of_inputs, 63);
+  if (!allocate_gpu_memory || bytes == 0) return;  // NULL: cuda_extract_bits_64 takes pool scratch
+  set_device(gpu_index);
+  keep_pool_memory();
+  void* p = nullptr;
+  CHIP_CHECK(hipMallocAsync(&p, bytes, (hipStream_t)stream));
+  {
+    std::lock_guard<std::mutex> g(g_eb_mu);
+    g_eb_scratch[p] = bytes;
+  }
+  *bit_extract_buffer = (int8_t*)p;
+}
+
+void cleanup_cuda_extract_bits(void* stream, uint32_t gpu_index, int8_t** bit_extract_buffer) {
+  if (!bit_extract_buffer || !*bit_extract_buffer) return;
+  set_device(gpu_index);
+  {
+    std::lock_guard<std::mutex> g(g_eb_mu);
+    g_eb_scratch.erase(*bit_extract_buffer);
+  }
+  CHIP_CHECK(hipFreeAsync(*bit_extract_buffer, (hipStream_t)stream));
+  *bit_extract_buffer = nullptr;
+}
+
+void cuda_extract_bits_64(void* stream, uint32_t gpu_index, void* list_lwe_array_out, const void* lwe_array_in,
+                          int8_t* bit_extract_buffer, const void* ksk, const void* fourier_bsk,
+                          uint32_t number_of_bits, uint32_t delta_log, uint32_t lwe_dimension_in,
+                          uint32_t lwe_dimension_out, uint32_t glwe_dimension, uint32_t polynomial_size,
+                          uint32_t base_log_bsk, uint32_t level_count_bsk, uint32_t base_log_ksk,
+                          uint32_t level_count_ksk, uint32_t number_of_samples, uint32_t max_shared_memory) {
+  (void)max_shared_memory;
+  // a `dest` of cuda_convert_lwe_programmable_bootstrap_key_64 stands for its registered Fourier key;
+  // any other pointer is a caller-owned Fourier key
+  const void* f = fourier_bsk;
+  {
+    std::lock_guard<std::mutex> g(g_keys_mu);
+    auto it = g_keys.find(fourier_bsk);
+    if (it != g_keys.end()) {
+      const KeyEntry& e = it->second;
+      if (e.n != lwe_dimension_out || e.k != glwe_dimension || e.level != level_count_bsk || e.N != polynomial_size ||
+          e.gpu != gpu_index) {
+        set_error("bootstrapping key converted for n=%u k=%u level=%u N=%u on gpu %u, called with n=%u k=%u "
+                  "level=%u N=%u on gpu %u",
+                  e.n, e.k, e.level, e.N, e.gpu, lwe_dimension_out, glwe_dimension, level_count_bsk, polynomial_size,
+                  gpu_index);
+        die("cuda_extract_bits_64");
+      }
+      f = e.fourier;
+    }
+  }
+  uint64_t bytes = 0;
+  if (bit_extract_buffer) {
+    std::lock_guard<std::mutex> g(g_eb_mu);
+    auto it = g_eb_scratch.find(bit_extract_buffer);
+    if (it == g_eb_scratch.end()) {
+      set_error("buffer %p does not come from scratch_cuda_extract_bits_64", (void*)bit_extract_buffer);
+      die("cuda_extract_bits_64");
+    }
+    bytes = it->second;
+  }
+  const std::vector<uint32_t> nb(number_of_samples, number_of_bits), dl(number_of_samples, delta_log);
+  if (concrete_hip_extract_bits(stream, gpu_index, (uint64_t*)list_lwe_array_out, (const uint64_t*)lwe_array_in, f,
+                                (const uint64_t*)ksk, nb.data(), dl.data(), nullptr, lwe_dimension_in,
+                                lwe_dimension_out, glwe_dimension, polynomial_size, base_log_bsk, level_count_bsk,
+                                base_log_ksk, level_count_ksk, number_of_samples, bit_extract_buffer, bytes) != 0)
+    die("cuda_extract_bits_64");
 }
 
 }  // extern "C"

@@ -41,6 +41,18 @@ void release_std_source(const void* primary);
 const void* generic_companion_key(const void* primary, uint32_t n, uint32_t k, uint32_t level, uint32_t N,
                                   hipStream_t s);
 
+// abi.hip: the gates and the key choice of concrete_hip_pbs, for callers that launch several PBS on one
+// key (extract_bits.hip).  0, or the refusal's code with the message set; makes gpu_index current.
+// `generic`: launch with pbs_generic_launch on `key` (the companion), else pbs_launch.
+struct PbsKey {
+  const void* key;
+  uint32_t limbs;
+  bool generic;
+};
+int pbs_resolve_key(void* stream, uint32_t gpu_index, const void* fourier_bsk, uint32_t lwe_dimension,
+                    uint32_t glwe_dimension, uint32_t polynomial_size, uint32_t base_log, uint32_t level_count,
+                    PbsKey* out);
+
 // keycheck.hip: the exactness gate against the converted key's measured spectrum (round 6).
 // key_spectrum_record reads the max|G| the conversion kernels left in the sink (synchronises s),
 // records it for `dest`, and returns -2 when no base_log could use the key exactly; key_bound_check returns -2

@@ -103,6 +103,28 @@ void cuda_negate_lwe_ciphertext_vector_64(void *stream, uint32_t gpu_index, void
                                           const void *lwe_array_in, uint32_t input_lwe_dimension,
                                           uint32_t input_lwe_ciphertext_count);
 
+/* Bit extraction, stage 1 of the WoP-PBS (concrete-cuda rust_api/src/cuda_bind.rs:494-567; the CPU
+ * runtime's memref_wop_pbs_crt_buffer runs the same primitive per CRT block, lib/Runtime/wrappers.cpp:
+ * 934-965).  From each of number_of_samples LWE ciphertexts of dimension lwe_dimension_in = k N,
+ * number_of_bits bits starting at bit delta_log are extracted, most significant first: output row
+ * s * number_of_bits + j (lwe_dimension_out + 1 words) encrypts bit j of sample s times 2^63.  The input
+ * is not modified.  `lwe_dimension` of the scratch call is the small dimension (lwe_dimension_out);
+ * max_shared_memory is accepted and ignored.  fourier_bsk is the `dest` of
+ * cuda_convert_lwe_programmable_bootstrap_key_64, or a caller-owned Fourier key
+ * (concrete_hip_convert_bsk).  A scratch call with allocate_gpu_memory = false leaves NULL, and a NULL
+ * buffer makes the extraction take stream-ordered pool scratch.  Bad arguments abort. */
+void scratch_cuda_extract_bits_64(void *stream, uint32_t gpu_index, int8_t **bit_extract_buffer,
+                                  uint32_t glwe_dimension, uint32_t lwe_dimension, uint32_t polynomial_size,
+                                  uint32_t level_count, uint32_t number_of_inputs, uint32_t max_shared_memory,
+                                  bool allocate_gpu_memory);
+void cuda_extract_bits_64(void *stream, uint32_t gpu_index, void *list_lwe_array_out, const void *lwe_array_in,
+                          int8_t *bit_extract_buffer, const void *ksk, const void *fourier_bsk,
+                          uint32_t number_of_bits, uint32_t delta_log, uint32_t lwe_dimension_in,
+                          uint32_t lwe_dimension_out, uint32_t glwe_dimension, uint32_t polynomial_size,
+                          uint32_t base_log_bsk, uint32_t level_count_bsk, uint32_t base_log_ksk,
+                          uint32_t level_count_ksk, uint32_t number_of_samples, uint32_t max_shared_memory);
+void cleanup_cuda_extract_bits(void *stream, uint32_t gpu_index, int8_t **bit_extract_buffer);
+
 /* ------------------------------------------------------------------------------------------
  * Part 2: extensions (return 0 on success, < 0 on error; message via concrete_hip_last_error)
  * ------------------------------------------------------------------------------------------ */
@@ -113,7 +135,9 @@ void cuda_negate_lwe_ciphertext_vector_64(void *stream, uint32_t gpu_index, void
  *    concrete_hip_set_thread_spin_limit;
  * 5: round 6 — status slots recycled on stream destroy (concrete_hip_status_slots_in_use,
  *    concrete_hip_set_status_slot_cap), converted keys checked against the certified bound
- *    (concrete_hip_key_spectrum_max)). */
+ *    (concrete_hip_key_spectrum_max)).
+ * Bit extraction (cuda_extract_bits_64, concrete_hip_extract_bits*) was added without a new version:
+ * the value stays 5, and a caller finds the capability through concrete_hip_extract_bits_supported. */
 uint32_t concrete_hip_abi_version(void);
 /* thread-local message of the last failed concrete_hip_* call */
 const char *concrete_hip_last_error(void);
@@ -193,6 +217,35 @@ int concrete_hip_keyswitch(void *stream, uint32_t gpu_index, uint64_t *lwe_array
                            const uint64_t *lwe_input_indexes, const uint64_t *ksk, uint32_t lwe_dimension_in,
                            uint32_t lwe_dimension_out, uint32_t base_log, uint32_t level_count,
                            uint32_t num_samples);
+/* Bit extraction with a status code and per-row parameters.  number_of_bits, delta_log and
+ * out_row_offsets are HOST arrays of num_samples entries; everything else that is a pointer is device
+ * memory.  Row i yields number_of_bits[i] ciphertexts of dimension lwe_dimension_out, most significant
+ * bit first, in output rows out_row_offsets[i] .. + number_of_bits[i] - 1 of the sum(number_of_bits)-row
+ * output; out_row_offsets == NULL packs the blocks in input order.  The u64 result is bit-identical to the
+ * loop of concrete_hip_keyswitch and concrete_hip_pbs it replaces.  scratch: a 16-byte aligned device
+ * buffer of at least concrete_hip_extract_bits_scratch_bytes(..., max number_of_bits) bytes, or NULL for
+ * stream-ordered pool scratch.  Stream-ordered; no host synchronisation between the iterations.
+ * Checked before the first device call: -1 null pointer; -3 a row with number_of_bits == 0, delta_log == 0
+ * or delta_log + number_of_bits > 64, lwe_dimension_in != glwe_dimension * polynomial_size, output blocks
+ * that overlap or leave the output rows, a scratch buffer too small or misaligned; -2 parameters the
+ * PBS or the keyswitch does not take (also: a key that fails the PBS exactness gate).  Nothing is written
+ * by a refused call. */
+int concrete_hip_extract_bits(void *stream, uint32_t gpu_index, uint64_t *lwe_array_out, const uint64_t *lwe_array_in,
+                              const void *fourier_bsk, const uint64_t *ksk, const uint32_t *number_of_bits,
+                              const uint32_t *delta_log, const uint64_t *out_row_offsets, uint32_t lwe_dimension_in,
+                              uint32_t lwe_dimension_out, uint32_t glwe_dimension, uint32_t polynomial_size,
+                              uint32_t base_log_bsk, uint32_t level_count_bsk, uint32_t base_log_ksk,
+                              uint32_t level_count_ksk, uint32_t num_samples, void *scratch, uint64_t scratch_bytes);
+/* scratch bytes of a call on num_samples rows of at most max_number_of_bits (1 .. 63) bits each; 0 for
+ * num_samples == 0 or max_number_of_bits out of range.  Does not decrease with either. */
+uint64_t concrete_hip_extract_bits_scratch_bytes(uint32_t lwe_dimension_in, uint32_t lwe_dimension_out,
+                                                 uint32_t glwe_dimension, uint32_t polynomial_size,
+                                                 uint32_t num_samples, uint32_t max_number_of_bits);
+/* 1 when concrete_hip_pbs_supported(k, N, level_bsk, base_log_bsk) and concrete_hip_keyswitch_supported(
+ * level_ksk, base_log_ksk, lwe_dimension_in, lwe_dimension_out) both hold and lwe_dimension_in == k N */
+int concrete_hip_extract_bits_supported(uint32_t lwe_dimension_in, uint32_t lwe_dimension_out,
+                                        uint32_t glwe_dimension, uint32_t polynomial_size, uint32_t base_log_bsk,
+                                        uint32_t level_count_bsk, uint32_t base_log_ksk, uint32_t level_count_ksk);
 /* Fourier key registered for a `dest` of cuda_convert_lwe_programmable_bootstrap_key_64, or NULL */
 const void *concrete_hip_lookup_bsk(const void *bootstrapping_key);
 /* Release what the backend derived from device buffer `ptr` (a registered Fourier key whose `dest`
