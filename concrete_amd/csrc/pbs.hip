@@ -28,6 +28,8 @@
 // port once per workgroup instead of once per ciphertext.  The whole CMUX loop runs in one
 // launch with the workgroup in lockstep (one raw s_barrier per key group and per half-spectrum
 // exchange).
+// Full batches at l = 3 run pbs1024_pair_slot_kernel (below): the same ownership, the key products
+// split by frequency slot over the eight waves and the key held in registers instead of the ring.
 #include <type_traits>
 
 #include "common.hpp"
@@ -519,8 +521,404 @@ pbs1024_pair_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
 }
 
 // ------------------------------------------------------------------------------------
+// pbs1024_pair_slot_kernel (l = 3, 4 ciphertexts per workgroup): the pair kernel with the key
+// shared in registers instead of through the LDS ring.
+//
+// Wave w = 2 ct + h owns polynomial h of ciphertext ct exactly as above (negated accumulator,
+// rotation, decomposition, the three forward and three inverse transforms, recombination, sample
+// extract), with fft512's natural slot order in every wave (no k2 ^ 4 relabeling).  Only the key
+// products are split differently: fft512 leaves 8 frequency slots per lane and the workgroup has 8
+// waves, so wave w takes slot k2 = w of all four ciphertexts, both input rows and both output
+// polynomials.  A key value then serves four ciphertexts from one register: it is loaded straight
+// from L2 with plain 16-byte-per-lane global loads (36 per wave and step, the bytes the ring's DMA
+// moved) — no ring, no LDS-DMA, no key-window barriers.
+//
+// Key addressing (bsk.hip): group (limb, co, ro) holds at slot p < 4 column co / row ro and at
+// slot p >= 4 column 1 - co / row 1 - ro, so wave w reads (column c, row r) of its slot from group
+// (limb, c ^ f, r ^ f), f = (w >= 4): group index 2 c + r for f = 0, 3 - (2 c + r) for f = 1.
+// A step's 36 values are taken in the order t = (limb, c, level q, r) (SLOT_QMAJOR) through a ring of
+// SLOT_PF registers: value t + SLOT_PF is requested when value t has been used.
+//
+// Exchanges go through one 8 KB mailbox per wave (next to its transpose scratch):
+//   forward:             levels 0 and 1 together — level 0 waits in registers during the second
+//                        transform, then v[0..7] -> own mailbox and level 1 -> own transpose
+//                        scratch (idle between transforms) | workgroup barrier | every wave reads
+//                        its slot from the 8 mailboxes and 8 scratches; level 2 through the
+//                        mailbox alone | workgroup barrier | reads
+//   products, per limb:  Y[ct][co] -> mailbox of wave (ct, co) at position w | workgroup barrier |
+//                        the wave reads its 8 slots; limb li + 1's first product window; inverse
+//                        and recombination of limb li
+// 5 workgroup barriers per step.  A mailbox (or published scratch) is written again only once
+// every wave has issued the reads of the previous exchange: each wave adds 1 to one LDS counter
+// after its reads (LDS operations of a wave execute in issue order) and writers wait for
+// 8 x (exchanges so far) with spin_until_ge; a transform or a product window lies between, so the
+// first poll normally passes.  (A step's first exchange needs no wait: the last readers of a
+// mailbox were its owner, and the scratch was released before the third transform.)
+// ------------------------------------------------------------------------------------
+#ifndef SLOT_PF
+#define SLOT_PF 6  // key values in flight per wave (a divisor of 36; 6 = one (limb, output) window)
+#endif
+#ifndef SLOT_FWD_PAIR
+#define SLOT_FWD_PAIR 1  // forward levels 0 and 1 traded in one exchange (5 barriers per step): +1.4 %
+#endif
+#ifndef SLOT_Y_EARLY
+#define SLOT_Y_EARLY 1  // limb li + 1's first product window ahead of limb li's inverse: +3.2 %
+#endif
+#ifndef SLOT_QMAJOR
+#define SLOT_QMAJOR 1  // products of a window in (level, row) order instead of (row, level): +0.4 %
+#endif
+#ifndef SLOT_DEFAULT
+#define SLOT_DEFAULT 1  // the planned call's pair part runs the slot-split kernel
+#endif
+constexpr int SLOT_MBOX = 512;// complex values per mailbox: 8 slots x 64 lanes
+constexpr size_t pbs1024_pair_slot_lds_bytes() {
+  return PBS1024_TABLE_BYTES + 2 * (size_t)PBS_PAIRS * (PBS1024_XCH_SLOTS + SLOT_MBOX) * 16 + 16;  // + the counter
+}
+
+__device__ __forceinline__ void slot_signal(uint32_t* ctr, int lane, uint32_t& cnt) {
+  asm volatile("" ::: "memory");
+  ++cnt;
+  if (lane == 0) __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+template <bool RESID, bool STAMPS>
+__global__ void __launch_bounds__(PBS_PAIRS * 128, 2)
+pbs1024_pair_slot_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_idx,
+                         const uint64_t* __restrict__ luts, const uint64_t* __restrict__ lut_idx,
+                         const uint64_t* __restrict__ in, const uint64_t* __restrict__ in_idx,
+                         const cplx* __restrict__ fbsk, uint32_t n, uint32_t base_log, uint32_t num_samples,
+                         unsigned long long* __restrict__ resid_out, SyncGuard guard) {
+  constexpr int K = 1, K1 = 2, N = 1024, LOG2_2N = 11, LIMBS = 3, L = 3, P = PBS_PAIRS, NW = 2 * P;
+  constexpr int GROUP = L * 512;                  // one (limb, co, ro) group: the L level spectra
+  constexpr int PER_I = K1 * K1 * LIMBS * GROUP;  // complex values per Fourier GGSW
+  constexpr int NKEY = LIMBS * K1 * K1 * L;       // key values per wave and step
+  constexpr int PF = SLOT_PF;
+  constexpr int XS = (int)PBS1024_XCH_SLOTS, MB = SLOT_MBOX;
+  static_assert(NW == 8, "one frequency slot per wave");
+  static_assert(NKEY % PF == 0, "a key value's register must not depend on the step");
+  static_assert(XCH_SLOTS <= XS, "transpose scratch");
+
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  cplx* tbl = reinterpret_cast<cplx*>(smem);                      // FFT tables (fft512.hpp)
+  cplx* xch_all = tbl + FFT512_TABLE_ENTRIES;                     // NW transpose scratches
+  cplx* mbox_all = xch_all + NW * XS;                             // NW mailboxes
+  uint32_t* ctr = reinterpret_cast<uint32_t*>(mbox_all + NW * MB);  // reads-issued counter
+
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int h = w & 1;  // polynomial
+  const int lane = threadIdx.x & 63;
+  const uint32_t s = blockIdx.x * P + (w >> 1);
+  const bool active = s < num_samples;
+  cplx* xch = xch_all + w * XS;
+  uint64_t* xch64 = reinterpret_cast<uint64_t*>(xch);
+  cplx* mybox = mbox_all + w * MB + lane;             // + k2 * 64
+  cplx* slotbox = mbox_all + w * 64 + lane;           // + u * MB: slot w of wave u's mailbox
+
+  // ---- key value t of a step (t = (limb K1 + c) K1 L + e, e in window order), for this wave's slot
+  const bool flip = w >= 4;
+  const cplx* key_w = fbsk + (w * 64 + (flip ? 3 * GROUP : 0));
+  const int gstride = flip ? -GROUP : GROUP;
+  auto key_load = [&](const cplx* key_step, int t) __attribute__((always_inline)) {
+    const int li = t / (K1 * K1 * L), co = t / (K1 * L) % K1, e = t % (K1 * L);
+    const int ro = SLOT_QMAJOR ? e % K1 : e / L, q = SLOT_QMAJOR ? e / K1 : e % L, cr = co * K1 + ro;
+    return (key_step + (li * K1 * K1 * GROUP + q * 512) + cr * gstride)[lane];
+  };
+  cplx g[PF] = {};
+  if (n > 0) {
+#pragma unroll
+    for (int t = 0; t < PF; ++t) g[t] = key_load(key_w, t);
+  }
+
+  build_fft512_tables(tbl, threadIdx.x, P * 128);
+  if (threadIdx.x == 0) *ctr = 0u;
+  uint32_t rcnt = 0;  // exchanges whose reads this wave has issued
+  __syncthreads();
+  const Fft512Tables T = fft512_tables_at(tbl);
+
+  const uint64_t* lwe = in + (active ? (in_idx ? in_idx[s] : s) : 0) * (uint64_t)(n + 1);
+  const uint64_t* lut = luts + (active && lut_idx ? lut_idx[s] : 0ull) * (uint64_t)(K1 * N);
+
+  // B = -acc_h, acc_h = LUT_h * X^{-ms(b)} (pbs1024_pair_kernel).  A wave of a missing ciphertext
+  // keeps B = 0 and still runs every barrier, counter and slot product of the others.
+  uint64_t B[16];
+  {
+    const uint32_t bt = active ? modswitch(lwe[n], LOG2_2N) : 0u;
+#pragma unroll
+    for (int m = 0; m < 16; ++m) {
+      const uint32_t src = (uint32_t)(lane + 64 * m + bt) & (2 * N - 1);
+      const uint64_t v = active ? lut[h * N + (src & (N - 1))] : 0ull;
+      B[m] = src < N ? 0ull - v : v;
+    }
+  }
+
+  const int nrep = 64 - L * (int)base_log;
+  const int logB = (int)base_log;
+  const int32_t neg_base = -(1 << logB);
+  const uint32_t half_m1 = (1u << (logB - 1)) - 1u;
+  double max_resid = 0.0;
+  // diagnostic stamps (STAMPS builds only): 0 rotation, 1 forward + exchange, 2 products,
+  // 5 barrier wait, 3 Y exchange, 4 inverse + recombination, 6 total, 7 work steps
+  uint64_t acc_t[NSTAMP] = {};
+  uint64_t t_begin = 0, tp = 0;
+  auto lap = [&](int k) __attribute__((always_inline)) {
+    if constexpr (STAMPS) {
+      const uint64_t t = stamp();
+      acc_t[k] += t - tp;
+      tp = t;
+    }
+  };
+  if constexpr (STAMPS) t_begin = stamp();
+
+  cplx tw3[4];  // forward pass-3 twiddles of my lane, in registers for the whole kernel
+  fwd_p3_tw(tw3, T, lane);
+
+  uint64_t a_next = active && n > 0 ? lwe[0] : 0ull;
+  for (uint32_t i = 0; i < n; ++i) {
+    const cplx* key_step = key_w + (uint64_t)i * PER_I;
+    const cplx* key_next = i + 1 < n ? key_step + PER_I : key_step;  // past the last step: re-read (unused)
+    const uint64_t ai = a_next;
+    if (i + 1 < n) a_next = active ? lwe[i + 1] : 0ull;
+    const uint32_t at = modswitch(ai, LOG2_2N);
+    if constexpr (STAMPS) {
+      tp = stamp();
+      acc_t[7] += ai != 0ull && at != 0u;
+    }
+
+    // ---- ct1 = B - X^{at} B and the decomposer state (pbs1024_pair_kernel)
+    uint32_t st[16];
+    {
+#pragma unroll
+      for (int m = 0; m < 16; ++m) xch64[lane + 64 * m] = B[m];
+      wave_lds_fence();
+      const uint32_t o0 = ((uint32_t)(lane - (int)at) << 3) + 8u * N;
+      const uint32_t khi = 1u << (nrep - 33);
+      uint64_t rv[16];
+#pragma unroll
+      for (int m = 0; m < 16; ++m)
+        rv[m] = *reinterpret_cast<const uint64_t*>(reinterpret_cast<const char*>(xch64) + ((o0 + 512u * m) & 8191u));
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int m = 0; m < 16; ++m) {
+        const uint32_t o = o0 + 512u * m;
+        const uint32_t s32 = (uint32_t)((int32_t)(o << 18) >> 31);
+        const uint64_t rvs = rv[m] ^ (((uint64_t)s32 << 32) | s32);
+        const uint64_t x = B[m] + rvs + (uint64_t)(s32 & 1u);
+        st[m] = ((uint32_t)(x >> 32) + khi) >> (nrep - 32);
+      }
+      wave_lds_fence();
+    }
+    lap(0);
+
+    // ---- forward transforms of my polynomial, one level at a time; X[q][u]: slot w of the
+    //      level-q spectrum of wave u (ciphertext u / 2, row u % 2)
+    cplx X[L][NW];
+    cplx hold[8];  // SLOT_FWD_PAIR: the level-0 spectrum during the second transform
+    (void)hold;
+#pragma unroll
+    for (int q = 0; q < L; ++q) {
+      cplx v[8];
+      int32_t d[16];
+#pragma unroll
+      for (int m = 0; m < 16; ++m)
+        d[m] = decomp_level32(st[m], (uint32_t)(q * logB), logB, half_m1, neg_base, q + 1 < L);
+#pragma unroll
+      for (int m = 0; m < 8; ++m) v[m] = {(double)d[m], (double)d[m + 8]};
+      cplx tw2[4];
+      fwd_p2_tw(tw2, T, lane >> 3);
+      if (FWD_TW2_EARLY) __builtin_amdgcn_sched_barrier(0);
+#if SLOT_FWD_PAIR
+      // Levels 0 and 1 are traded in one exchange: level 0 waits in registers during the second
+      // transform, then goes to my mailbox and level 1 to my transpose scratch (idle between
+      // transforms).  The third transform overwrites that scratch, so it first waits (right
+      // before its first LDS write) until every wave has read the pair.
+      fft512_fwd_tw(v, xch, lane, tw2, tw3, 0ull, [&]() __attribute__((always_inline)) {
+        if (q == 2) spin_until_ge(ctr, NW * rcnt, guard);
+      });
+      if (q == 0) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) hold[k] = v[k];
+      } else {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          if (q == 1) mybox[k * 64] = hold[k], xch[k * 64 + lane] = v[k];
+          else mybox[k * 64] = v[k];
+        }
+        lap(1);
+        pair_barrier();
+        lap(5);
+#pragma unroll
+        for (int u = 0; u < NW; ++u) {
+          if (q == 1) X[0][u] = slotbox[u * MB], X[1][u] = xch_all[u * XS + w * 64 + lane];
+          else X[2][u] = slotbox[u * MB];
+        }
+        slot_signal(ctr, lane, rcnt);
+      }
+#else
+      fft512_fwd_tw(v, xch, lane, tw2, tw3, 0ull, []() __attribute__((always_inline)) {});
+      // every wave has read the previous level from my mailbox
+      if (q > 0) spin_until_ge(ctr, NW * rcnt, guard);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) mybox[k * 64] = v[k];
+      lap(1);
+      pair_barrier();
+      lap(5);
+#pragma unroll
+      for (int u = 0; u < NW; ++u) X[q][u] = slotbox[u * MB];
+      slot_signal(ctr, lane, rcnt);
+#endif
+    }
+    lap(1);
+
+    // ---- per limb: products of my slot for the 4 ciphertexts and both outputs (key from
+    //      registers, refilled PF values ahead), Y exchange, inverse of my polynomial.
+    auto recombine = [&](const cplx (&v)[8], auto LIc) __attribute__((always_inline)) {
+      constexpr int lr = decltype(LIc)::value;
+#pragma unroll
+      for (int m = 0; m < 8; ++m) {
+        const double tr = RND_MAGIC - v[m].re, ti = RND_MAGIC - v[m].im;
+        if constexpr (RESID) {
+          max_resid = fmax(max_resid, fabs(v[m].re - (RND_MAGIC - tr)));
+          max_resid = fmax(max_resid, fabs(v[m].im - (RND_MAGIC - ti)));
+        }
+        if constexpr (lr == 0) {
+          B[m] += (uint64_t)__double_as_longlong(tr) - MAGIC_ALL;
+          B[m + 8] += (uint64_t)__double_as_longlong(ti) - MAGIC_ALL;
+        } else {
+          B[m] += (uint64_t)__double_as_longlong(tr) << limb_shift(lr);
+          B[m + 8] += (uint64_t)__double_as_longlong(ti) << limb_shift(lr);
+        }
+      }
+    };
+    // one product window: output co of limb li for the 4 ciphertexts, then into the mailboxes of
+    // the waves (ct, co) at my position.  Before a limb's first window is sent, every wave must
+    // have read the previous exchange (the last forward level, or the previous limb's Y).
+    auto window = [&](auto LIc, auto COc) __attribute__((always_inline)) {
+      constexpr int li = decltype(LIc)::value, co = decltype(COc)::value;
+      cplx Y[P];  // set by the first product (no zeroing)
+#pragma unroll
+      for (int e = 0; e < K1 * L; ++e) {
+        // row-major (ro, q), or SLOT_QMAJOR: level-major (q, ro), which needs the last forward
+        // level's spectra only in the last third of a window
+        const int ro = SLOT_QMAJOR ? e % K1 : e / L, q = SLOT_QMAJOR ? e / K1 : e % L;
+        const int t = (li * K1 + co) * K1 * L + e;
+        const cplx gv = g[t % PF];
+#pragma unroll
+        for (int c = 0; c < P; ++c) {
+          const cplx x = X[q][2 * c + ro];
+          if (e == 0) {  // fma(a, b, 0) == a * b: same bits as accumulating from 0
+            Y[c].re = __builtin_fma(x.re, gv.re, -x.im * gv.im);
+            Y[c].im = __builtin_fma(x.re, gv.im, x.im * gv.re);
+          } else {
+            Y[c].re = __builtin_fma(x.re, gv.re, __builtin_fma(-x.im, gv.im, Y[c].re));
+            Y[c].im = __builtin_fma(x.re, gv.im, __builtin_fma(x.im, gv.re, Y[c].im));
+          }
+        }
+        // refill: the loads of a step are spread over its six product windows (§4.11)
+        g[t % PF] = t + PF < NKEY ? key_load(key_step, t + PF) : key_load(key_next, t + PF - NKEY);
+      }
+#pragma unroll
+      for (int c = 0; c < P; ++c) pin(Y[c]);
+      if (co == 0) spin_until_ge(ctr, NW * rcnt, guard);
+#pragma unroll
+      for (int c = 0; c < P; ++c) mbox_all[(2 * c + co) * MB + w * 64 + lane] = Y[c];
+    };
+    // SLOT_Y_EARLY: the first window of limb li + 1 runs between the reads of limb li's Y and its
+    // inverse, so the reads' latency (and the other waves' reads, which that window's mailbox
+    // writes wait for) is covered by 96 FMAs instead of being exposed right behind the barrier.
+    if (SLOT_Y_EARLY) window(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
+    static_for<0, LIMBS>([&](auto LI) __attribute__((always_inline)) {
+      constexpr int li = decltype(LI)::value;
+      if (!SLOT_Y_EARLY) window(LI, std::integral_constant<int, 0>{});
+      window(LI, std::integral_constant<int, 1>{});
+      lap(2);
+      pair_barrier();
+      lap(5);
+      cplx vp[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) vp[k] = mybox[k * 64];
+      slot_signal(ctr, lane, rcnt);
+      lap(3);
+      if constexpr (SLOT_Y_EARLY && li + 1 < LIMBS) {
+        window(std::integral_constant<int, li + 1>{}, std::integral_constant<int, 0>{});
+        lap(2);
+      }
+      cplx gi2[4];  // inverse pass-2 stage twiddles, read ahead of the transpose
+      inv_p2_stage_tw(gi2, T, lane & 7);
+      fft512_inv_tw(vp, xch, T, lane, gi2, 0ull);
+      recombine(vp, LI);
+      // materialise B here (else the inverse tail sinks into the next limb's products)
+#pragma unroll
+      for (int m = 0; m < 16; ++m) pin(B[m]);
+      if constexpr (RESID) pin(max_resid);
+      lap(4);
+    });
+  }
+
+  if constexpr (STAMPS) {
+    acc_t[6] = stamp() - t_begin;
+    if (lane == 0 && resid_out) {
+      unsigned long long* dst = resid_out + ((uint64_t)blockIdx.x * NW + w) * NSTAMP;
+      for (int q = 0; q < NSTAMP; ++q) dst[q] = acc_t[q];
+    }
+  }
+
+  // ---- sample extract (nth = 0) of acc = -B (pbs1024_pair_kernel)
+  uint64_t* o = out + (active ? (out_idx ? out_idx[s] : s) : 0) * (uint64_t)(K * N + 1);
+  if (!active) {
+  } else if (h == 0) {
+#pragma unroll
+    for (int m = 0; m < 16; ++m) xch64[lane + 64 * m] = B[m];
+    wave_lds_fence();
+#pragma unroll
+    for (int m = 0; m < 16; ++m) {
+      const int j = lane + 64 * m;
+      const uint64_t v = xch64[(N - j) & (N - 1)];
+      o[j] = j == 0 ? 0ull - v : v;
+    }
+  } else if (lane == 0) {
+    o[K * N] = 0ull - B[0];
+  }
+
+  if constexpr (RESID && !STAMPS) {
+    for (int off = 32; off > 0; off >>= 1) max_resid = fmax(max_resid, __shfl_xor(max_resid, off));
+    if (lane == 0 && active && resid_out) atomicMax(resid_out, (unsigned long long)__double_as_longlong(max_resid));
+  }
+}
+
+// ------------------------------------------------------------------------------------
 // host launchers
 // ------------------------------------------------------------------------------------
+template <bool RESID, bool STAMPS>
+static int launch_slot_t(const PbsArgs& a) {
+  constexpr int P = PBS_PAIRS;
+  const size_t lds = pbs1024_pair_slot_lds_bytes();
+  static_assert(pbs1024_pair_slot_lds_bytes() <= 160 * 1024, "LDS of one CU");
+  if (!pbs1024_exact(1, 3, a.base_log)) {
+    set_error("pbs: N=1024 l=3 logB=%u is outside the exact range", a.base_log);
+    return -2;
+  }
+  auto kern = pbs1024_pair_slot_kernel<RESID, STAMPS>;
+  CHIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  const uint32_t blocks = (a.num_samples + P - 1) / P;
+  hipLaunchKernelGGL(kern, dim3(blocks), dim3(P * 128), lds, a.stream, a.out, a.out_idx, a.luts, a.lut_idx,
+                     a.in, a.in_idx, reinterpret_cast<const cplx*>(a.fbsk), a.n, a.base_log, a.num_samples, a.resid,
+                     a.guard);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    set_error("pbs launch failed: %s", hipGetErrorString(e));
+    return -1;
+  }
+  return 0;
+}
+
+// the slot-split kernel (4 ciphertexts per workgroup, l = 3); with CONCRETE_HIP_PBS_STAMPS=1 its
+// instrumented build (`resid`: 8 * ceil(num_samples / 4) * NSTAMP u64)
+static int launch_slot(const PbsArgs& a) {
+  static const bool stamps = getenv("CONCRETE_HIP_PBS_STAMPS") && atoi(getenv("CONCRETE_HIP_PBS_STAMPS"));
+  if (stamps) return launch_slot_t<true, true>(a);
+  return a.resid ? launch_slot_t<true, false>(a) : launch_slot_t<false, false>(a);
+}
+
 template <int P, int L, bool RESID, bool STAMPS>
 static int launch_pair_t(const PbsArgs& a) {
   const size_t lds = pbs1024_pair_lds_bytes(L, P);
@@ -605,7 +1003,14 @@ static int launch_pair(const PbsArgs& a) {
   // Round 6: the call is split over the kernels by pbs1024_plan.hpp (whole pair rounds, six-wave
   // rounds, at most one round of one ciphertext per workgroup), each part a contiguous range of the
   // batch launched on the caller's stream.
+  // The slot-split kernel (pbs1024_pair_slot_kernel): CONCRETE_HIP_PBS_SLOT=1 forces it for a whole
+  // call of any batch, =0 keeps the ring kernel in the plan's pair part (read per call: tests, A/B);
+  // unset, SLOT_DEFAULT decides.  Every other override keeps its meaning (CONCRETE_HIP_PBS_PAIRS=4 is
+  // the ring kernel: the A/B switch).
   if (L == 3) {
+    const char* se = getenv("CONCRETE_HIP_PBS_SLOT");
+    const int sl = se ? atoi(se) : -1;
+    if (sl == 1) return launch_slot(a);
     const char* he = getenv("CONCRETE_HIP_PBS_HEX");
     const int hx = he ? atoi(he) : -1;
     if (hx == 1 || hx == 2) return pbs1024_hex_launch(a, hx);
@@ -614,7 +1019,8 @@ static int launch_pair(const PbsArgs& a) {
       uint32_t start = 0;
       int rc = 0;
       if (plan.pair) {
-        rc = launch_pair_p<4, L>(pbs_args_range(a, start, plan.pair));
+        const PbsArgs part = pbs_args_range(a, start, plan.pair);
+        rc = (sl == 0 || !SLOT_DEFAULT) ? launch_pair_p<4, L>(part) : launch_slot(part);
         start += plan.pair;
       }
       if (rc == 0 && plan.hex2) {

@@ -23,9 +23,15 @@ t0 = torch.cuda.Event(enable_timing=True); t1 = torch.cuda.Event(enable_timing=T
 t0.record(); B.pbs(p, fbsk, d_in, d_lut, resid=buf); t1.record(); torch.cuda.synchronize()
 st = buf.cpu().numpy().reshape(nw, NS).astype(np.float64)
 names = ["rot+decomp", "fwd+xchg", "mac", "y-xchg", "inv+recomb", "ring-barrier", "total", "work_steps", "vmcnt-wait"]
+order = (0, 1, 2, 8, 3, 4, 5)
+kernel = "pbs1024_pair_kernel"
+if os.environ.get("CONCRETE_HIP_PBS_SLOT") == "1":  # the slot-split kernel ran: its phases in the same slots
+    kernel = "pbs1024_pair_slot_kernel"
+    names = ["rotation", "fwd+exchange", "products", "y-exchange", "inverse", "barrier-wait", "total", "work_steps", "-"]
+    order = (0, 1, 2, 5, 3, 4)
 tot = st[:, 6].mean()
-print(f"kernel {t0.elapsed_time(t1):.2f} ms (stamp build), batch {nb}, mean wave cycles {tot:.3g} (memtime ticks)")
-for k in (0, 1, 2, 8, 3, 4, 5):
+print(f"{kernel} {t0.elapsed_time(t1):.2f} ms (stamp build), batch {nb}, mean wave cycles {tot:.3g} (memtime ticks)")
+for k in order:
     nme = names[k]
     print(f"  {nme:14s} {st[:, k].mean() / tot * 100:6.1f} %   per step {st[:, k].mean() / p.n:9.0f}")
 print(f"  work steps {st[:, 7].mean():.1f}")
