@@ -1,4 +1,7 @@
-// kernel_util.hpp — device helpers shared by the PBS kernels (pbs.hip, pbs2048.hip).
+// kernel_util.hpp — device scaffolding shared by every fused PBS kernel (pbs.hip, pbs1024_quad.hip,
+// pbs1024_hex.hip, pbs2048.hip, pbs1024k2.hip, pbs_small.hip, pbs512k4.hip) and by pbs_generic.hip /
+// keyswitch.hip: the wave-group sync on LDS counters and its bounded spin, the LDS-DMA issue of a
+// key-ring group, the limb rounding constants and the RESID epilogue.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -6,6 +9,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "fft512.hpp"
 
 namespace chip {
 
@@ -21,6 +25,17 @@ __device__ __forceinline__ void static_for(F&& f) {
 // bits(v + 1.5 * 2^52) = bits(1.5 * 2^52) + round(v) for |v| < 2^51
 constexpr double RND_MAGIC = 6755399441055744.0;
 constexpr uint64_t RND_MAGIC_BITS = 0x4338000000000000ull;
+// sum over the key limbs of the rounding constant at each limb's shift (`bits` per limb): removed
+// once per recombination
+constexpr uint64_t limb_magic_all(int limbs, int bits) {
+  uint64_t m = 0;
+  for (int li = 0; li < limbs; ++li) m += RND_MAGIC_BITS << (bits * li);
+  return m;
+}
+// the N = 1024, k = 1 key's three balanced limbs of 22/21/21 bits: shifts 0, 22, 43
+constexpr int limb_shift(int li) { return li * 21 + (li > 0 ? 1 : 0); }
+constexpr uint64_t MAGIC_ALL_3 =
+    (RND_MAGIC_BITS << limb_shift(0)) + (RND_MAGIC_BITS << limb_shift(1)) + (RND_MAGIC_BITS << limb_shift(2));
 
 // Workgroup barrier for the two waves of a ciphertext: LDS writes drained, compiler fence,
 // no vmcnt drain (key loads may stay in flight).
@@ -43,6 +58,80 @@ __device__ __forceinline__ void spin_until_ge(const uint32_t* ctr, uint32_t targ
   }
   asm volatile("" ::: "memory");
 }
+// The same wait on counters ctr[0 .. NC) at once: the NC reads are issued together per poll.
+// (The cooperative kernel's grid-wide wait, pbs_generic.hip gen_coop_kernel, polls from lane 0 only
+// and keeps its own loop.)
+template <int NC>
+__device__ __forceinline__ void spin_until_all_ge(const uint32_t* ctr, uint32_t target, const SyncGuard& guard) {
+  for (uint32_t it = 0;; ++it) {
+    uint32_t lo = 0xffffffffu;
+#pragma unroll
+    for (int o = 0; o < NC; ++o) {
+      const uint32_t x = __hip_atomic_load(ctr + o, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      lo = x < lo ? x : lo;
+    }
+    if (lo >= target) break;
+    if (it >= guard.spin_limit) {
+      __hip_atomic_fetch_or(guard.status, DEV_STATUS_SYNC_TIMEOUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      break;
+    }
+    __builtin_amdgcn_s_sleep(0);
+  }
+  asm volatile("" ::: "memory");
+}
+
+// Synchronisation of the G waves that share one ciphertext, on G LDS counters f[0 .. G): wave v of
+// the group publishes in f[v] how many sync points it has passed and waits until its G - 1
+// partners, visited in the order v + 1, v + 2, ... (mod G), have reached the same count, so the
+// other ciphertexts of the workgroup are not held up as they would be by s_barrier.
+// Only LDS traffic is drained (lgkmcnt), never the key DMA: the store is relaxed, since a release
+// fence would add vmcnt(0).  LDS operations are coherent across the waves of a CU, and those of
+// one wave execute in issue order, which is what the split form relies on: group_signal, placed
+// after this wave's reads of its partners' scratch, is seen only after those reads; group_wait,
+// placed before this wave next overwrites its own scratch, waits for the partners' signals.
+// group_sync is the full exchange point (my LDS writes drained, then signal and wait in one).
+template <int G>
+__device__ __forceinline__ int group_partner(int v, int o) {
+  static_assert(G == 3 || (G & (G - 1)) == 0, "group sizes in use");
+  if constexpr (G == 2) return v ^ 1;
+  else if constexpr ((G & (G - 1)) == 0) return (v + o) & (G - 1);
+  else return o == 1 ? (v == G - 1 ? 0 : v + 1) : (v == 0 ? G - 1 : v - 1);  // G = 3
+}
+template <int G>
+__device__ __forceinline__ void group_signal(uint32_t* f, int v, uint32_t& cnt) {
+  asm volatile("" ::: "memory");
+  ++cnt;
+  __hip_atomic_store(&f[v], cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+template <int G>
+__device__ __forceinline__ void group_wait(const uint32_t* f, int v, uint32_t cnt, const SyncGuard& guard) {
+#pragma unroll
+  for (int o = 1; o < G; ++o) spin_until_ge(&f[group_partner<G>(v, o)], cnt, guard);
+  asm volatile("" ::: "memory");
+}
+template <int G>
+__device__ __forceinline__ void group_sync(uint32_t* f, int v, uint32_t& cnt, const SyncGuard& guard) {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  ++cnt;
+  __hip_atomic_store(&f[v], cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+#pragma unroll
+  for (int o = 1; o < G; ++o) spin_until_ge(&f[group_partner<G>(v, o)], cnt, guard);
+}
+// group_sync composed from the split form (two more compiler fences, which move the scheduler's
+// choices): the form pbs512k4.hip and the many-level kernel of pbs1024k2.hip were tuned with
+template <int G>
+__device__ __forceinline__ void group_sync_composed(uint32_t* f, int v, uint32_t& cnt, const SyncGuard& guard) {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  group_signal<G>(f, v, cnt);
+  group_wait<G>(f, v, cnt, guard);
+}
+
+// RESID tail of every fused kernel: this wave's largest rounding residual |x - round(x)| folded into
+// *resid_out (the bits of a non-negative double order as an unsigned integer)
+__device__ __forceinline__ void report_resid(double max_resid, int lane, bool active, unsigned long long* resid_out) {
+  for (int off = 32; off > 0; off >>= 1) max_resid = fmax(max_resid, __shfl_xor(max_resid, off));
+  if (lane == 0 && active && resid_out) atomicMax(resid_out, (unsigned long long)__double_as_longlong(max_resid));
+}
 
 // Diagnostic cycle stamps (STAMPS builds only; never in the product kernel).
 __device__ __forceinline__ uint64_t stamp() {
@@ -55,6 +144,33 @@ __device__ __forceinline__ uint64_t stamp() {
 constexpr int NSTAMP = 10;  // rot+decomp, fwd+xchg, mac, y-xchg, inv+recomb, ring barrier, total, steps, vmcnt, -
 
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
+
+// LDS-DMA of this wave's GLDS 1 KB pieces of one key-ring group: piece j goes from src + 1024 j
+// (16 bytes per lane, lane_b = 16 lane) to dst + 64 j.  The caller orders the ring with explicit
+// vmcnt waits and workgroup barriers.
+// VIA_ASM: issued from inline assembly so that the compiler does not see an LDS write: with the
+// builtin it treats every window's key reads as possibly aliasing the DMA and waits for all of
+// them (lgkmcnt(0)) before the first FMA; this way it counts them (lgkmcnt(4) ...): +1.1 % PBS/s
+// in pbs1024_pair_kernel.  M0 (the LDS base of the piece) is set inside the statement; nothing
+// else in these kernels uses M0.
+// (Arguments by reference: by value, pbs512k4.hip's builtin form came out with an M0 write per
+// piece, 818 instead of 524 in the file.)
+template <int GLDS, bool VIA_ASM>
+__device__ __forceinline__ void ring_issue(const char* const& src, cplx* const& dst, const uint32_t& lane_b) {
+#pragma unroll
+  for (int j = 0; j < GLDS; ++j) {
+    const cplx* gp = reinterpret_cast<const cplx*>(src + j * 1024 + lane_b);
+    if constexpr (VIA_ASM) {
+      const uint32_t m0 = (uint32_t)(uintptr_t)(lds_ptr_t)(dst + j * 64);
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"
+      asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dwordx4 %0, off" : : "v"(gp), "s"(m0) : "m0", "memory");
+#pragma clang diagnostic pop
+    } else {
+      __builtin_amdgcn_global_load_lds(gp, (lds_ptr_t)(dst + j * 64), 16, 0, 0);
+    }
+  }
+}
 
 // Optimisation barrier on a register value: the value is computed here and not later (the
 // compiler otherwise sinks pure arithmetic past LDS barriers into later phases, where its

@@ -38,12 +38,12 @@
 #include "pbs.hpp"
 #include "pbs1024_plan.hpp"
 #include "pbs_hex.hpp"
+#include "pbs_launch.hpp"
 
 namespace chip {
 
-// sum over limbs of RND_MAGIC_BITS << shift(limb), LIMBS = 3 (shifts 0, 22, 43)
-constexpr uint64_t MAGIC_ALL = RND_MAGIC_BITS + (RND_MAGIC_BITS << 22) + (RND_MAGIC_BITS << 43);
-constexpr int limb_shift(int li) { return li * 21 + (li > 0 ? 1 : 0); }
+static_assert(MAGIC_ALL_3 == RND_MAGIC_BITS + (RND_MAGIC_BITS << 22) + (RND_MAGIC_BITS << 43),
+              "three limbs at shifts 0, 22, 43");
 
 #ifndef FWD_LAST_VIA_WINDOW
 #define FWD_LAST_VIA_WINDOW 1  // last forward exchange published by the first key window's barrier
@@ -62,43 +62,24 @@ constexpr int limb_shift(int li) { return li * 21 + (li > 0 ? 1 : 0); }
 #define PAIR_FLAGS 1  // half-spectrum exchanges synchronise the two waves of a pair only
 #endif
 
-// Synchronisation point of the half-spectrum exchanges.  PAIR_FLAGS: a pair-local barrier on
-// LDS counters — each wave publishes how many sync points it has passed and waits for its
-// partner to reach the same count — so the other pairs of the workgroup are not held up.
-// Only LDS traffic is drained (lgkmcnt), never the key DMA (no release fence: that would add
-// vmcnt(0)).  LDS operations are coherent across the waves of a CU.
-// (DIAG_NOXBAR: timing-only builds without any exchange synchronisation.)
-// Split form: pair_signal publishes that this wave has issued its reads of the partner's
-// scratch (LDS operations of a wave execute in issue order, so the count is seen only after
-// them); pair_wait, before this wave next overwrites its own scratch, waits for the partner's.
-__device__ __forceinline__ void pair_signal(uint32_t* flags, int w, uint32_t& cnt) {
-  asm volatile("" ::: "memory");
-  ++cnt;
-#if !defined(DIAG_NOXBAR)
-  __hip_atomic_store(&flags[w], cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#endif
-}
-__device__ __forceinline__ void pair_wait(uint32_t* flags, int w, uint32_t cnt, const SyncGuard& guard) {
+// Sync group (kernel_util.hpp group_*<2>): the two waves of a pair, f = the pair's counters, h = my
+// polynomial.  DIAG_NOXBAR: timing-only builds without any exchange synchronisation; PAIR_FLAGS = 0:
+// the half-spectrum exchanges hold up the whole workgroup instead.
 #if defined(DIAG_NOXBAR)
-  (void)flags, (void)w, (void)cnt, (void)guard;
+constexpr bool XBAR = false;
 #else
-  spin_until_ge(&flags[w ^ 1], cnt, guard);
+constexpr bool XBAR = true;
 #endif
-  asm volatile("" ::: "memory");
+__device__ __forceinline__ void pair_signal(uint32_t* f, int h, uint32_t& cnt) {
+  if constexpr (XBAR) group_signal<2>(f, h, cnt);
 }
-__device__ __forceinline__ void xchg_barrier(uint32_t* flags, int w, uint32_t& cnt, const SyncGuard& guard) {
-#if defined(DIAG_NOXBAR)
-  (void)flags, (void)w, (void)cnt, (void)guard;
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#elif PAIR_FLAGS
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  ++cnt;
-  __hip_atomic_store(&flags[w], cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  spin_until_ge(&flags[w ^ 1], cnt, guard);
-#else
-  (void)flags, (void)w, (void)cnt, (void)guard;
-  pair_barrier();
-#endif
+__device__ __forceinline__ void pair_wait(uint32_t* f, int h, uint32_t cnt, const SyncGuard& guard) {
+  if constexpr (XBAR) group_wait<2>(f, h, cnt, guard);
+}
+__device__ __forceinline__ void xchg_barrier(uint32_t* f, int h, uint32_t& cnt, const SyncGuard& guard) {
+  if constexpr (!XBAR) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  else if constexpr (PAIR_FLAGS) group_sync<2>(f, h, cnt, guard);
+  else pair_barrier();
 }
 
 template <int P, int L, bool RESID, bool STAMPS>
@@ -126,6 +107,7 @@ pbs1024_pair_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
 
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int h = w & 1;  // polynomial = frequency half
+  uint32_t* pf = pflags + (w - h);  // my pair's two counters
   const uint64_t hsign = (uint64_t)h << 63;  // sign mask of the k2 ^ 4 relabeling (h = 1)
   const int lane = threadIdx.x & 63;
   const uint32_t s = blockIdx.x * P + (w >> 1);
@@ -148,24 +130,7 @@ pbs1024_pair_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
   cplx* ring_w = ring + w * GLDS * 64;
   const uint32_t lane_b = (uint32_t)lane * (uint32_t)sizeof(cplx);  // zero-extended lane offset
   auto issue_group = [&](const cplx* key_step, int r) __attribute__((always_inline)) {
-    const char* src = reinterpret_cast<const char*>(key_step + r * GROUP);
-    cplx* dst = ring_w + (r % 3) * GROUP;
-#pragma unroll
-    for (int j = 0; j < GLDS; ++j)
-    {
-      // Issued from inline assembly so that the compiler does not see an LDS write: with the
-      // builtin it treats every window's key reads as possibly aliasing the DMA and waits for
-      // all twelve (lgkmcnt(0)) before the first FMA; here it counts them (lgkmcnt(4) ...):
-      // +1.1 % PBS/s.  The ring is ordered by the explicit vmcnt waits and workgroup barriers
-      // alone.  M0 (the LDS base of the piece) is set inside the statement; nothing else in the
-      // kernel uses M0.
-      const cplx* gp = reinterpret_cast<const cplx*>(src + j * 1024 + lane_b);
-      const uint32_t m0 = (uint32_t)(uintptr_t)(lds_ptr_t)(dst + j * 64);
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-      asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dwordx4 %0, off" : : "v"(gp), "s"(m0) : "m0", "memory");
-#pragma clang diagnostic pop
-    }
+    ring_issue<GLDS, true>(reinterpret_cast<const char*>(key_step + r * GROUP), ring_w + (r % 3) * GROUP, lane_b);
   };
   if (n > 0) {
     issue_group(key_w, 0);
@@ -296,7 +261,7 @@ pbs1024_pair_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
             // round trip per stage)
             if (FWD_TW2_EARLY) __builtin_amdgcn_sched_barrier(0);
             fft512_fwd_tw(v, xch, lane, tw2, tw3, hsign, [&]() __attribute__((always_inline)) {
-              if (q0 > 0 && t == 0) pair_wait(pflags, w, pcnt, guard);
+              if (q0 > 0 && t == 0) pair_wait(pf, h, pcnt, guard);
             });
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -316,7 +281,7 @@ pbs1024_pair_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
       // second window (row 1); they are read right after that barrier.
       const bool last_batch = q0 + XB >= L;
       if (!last_batch || !FWD_LAST_VIA_WINDOW) {
-        xchg_barrier(pflags, w, pcnt, guard);
+        xchg_barrier(pf, h, pcnt, guard);
 #pragma unroll
         for (int t = 0; t < XB; ++t)
           if (t < nq)
@@ -332,7 +297,7 @@ pbs1024_pair_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
       // my partner's mailbox has been read: signal it (it waits before its next transform writes
       // its scratch).  After the last batch the scratch is next written behind the key windows'
       // workgroup barriers.
-      if (q0 + XB < L) pair_signal(pflags, w, pcnt);
+      if (q0 + XB < L) pair_signal(pf, h, pcnt);
     }
     if constexpr (STAMPS) {
       uint64_t t = stamp();
@@ -355,8 +320,8 @@ pbs1024_pair_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
           max_resid = fmax(max_resid, fabs(v[m].im - (RND_MAGIC - ti)));
         }
         if constexpr (lr == 0) {
-          B[m] += (uint64_t)__double_as_longlong(tr) - MAGIC_ALL;
-          B[m + 8] += (uint64_t)__double_as_longlong(ti) - MAGIC_ALL;
+          B[m] += (uint64_t)__double_as_longlong(tr) - MAGIC_ALL_3;
+          B[m + 8] += (uint64_t)__double_as_longlong(ti) - MAGIC_ALL_3;
         } else {
           B[m] += (uint64_t)__double_as_longlong(tr) << limb_shift(lr);
           B[m + 8] += (uint64_t)__double_as_longlong(ti) << limb_shift(lr);
@@ -456,7 +421,7 @@ pbs1024_pair_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
         acc_t[2] += t - tp;
         tp = t;
       }
-      xchg_barrier(pflags, w, pcnt, guard);
+      xchg_barrier(pf, h, pcnt, guard);
       // my output polynomial's spectrum, slots in order k2 ^ 4h (undone by the inverse pass 1)
       cplx vp[8];
 #pragma unroll
@@ -514,10 +479,7 @@ pbs1024_pair_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
     o[K * N] = 0ull - B[0];
   }
 
-  if constexpr (RESID && !STAMPS) {
-    for (int off = 32; off > 0; off >>= 1) max_resid = fmax(max_resid, __shfl_xor(max_resid, off));
-    if (lane == 0 && active && resid_out) atomicMax(resid_out, (unsigned long long)__double_as_longlong(max_resid));
-  }
+  if constexpr (RESID && !STAMPS) report_resid(max_resid, lane, active, resid_out);
 }
 
 // ------------------------------------------------------------------------------------
@@ -781,8 +743,8 @@ pbs1024_pair_slot_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict_
           max_resid = fmax(max_resid, fabs(v[m].im - (RND_MAGIC - ti)));
         }
         if constexpr (lr == 0) {
-          B[m] += (uint64_t)__double_as_longlong(tr) - MAGIC_ALL;
-          B[m + 8] += (uint64_t)__double_as_longlong(ti) - MAGIC_ALL;
+          B[m] += (uint64_t)__double_as_longlong(tr) - MAGIC_ALL_3;
+          B[m + 8] += (uint64_t)__double_as_longlong(ti) - MAGIC_ALL_3;
         } else {
           B[m] += (uint64_t)__double_as_longlong(tr) << limb_shift(lr);
           B[m + 8] += (uint64_t)__double_as_longlong(ti) << limb_shift(lr);
@@ -879,10 +841,7 @@ pbs1024_pair_slot_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict_
     o[K * N] = 0ull - B[0];
   }
 
-  if constexpr (RESID && !STAMPS) {
-    for (int off = 32; off > 0; off >>= 1) max_resid = fmax(max_resid, __shfl_xor(max_resid, off));
-    if (lane == 0 && active && resid_out) atomicMax(resid_out, (unsigned long long)__double_as_longlong(max_resid));
-  }
+  if constexpr (RESID && !STAMPS) report_resid(max_resid, lane, active, resid_out);
 }
 
 // ------------------------------------------------------------------------------------
@@ -897,18 +856,7 @@ static int launch_slot_t(const PbsArgs& a) {
     set_error("pbs: N=1024 l=3 logB=%u is outside the exact range", a.base_log);
     return -2;
   }
-  auto kern = pbs1024_pair_slot_kernel<RESID, STAMPS>;
-  CHIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const uint32_t blocks = (a.num_samples + P - 1) / P;
-  hipLaunchKernelGGL(kern, dim3(blocks), dim3(P * 128), lds, a.stream, a.out, a.out_idx, a.luts, a.lut_idx,
-                     a.in, a.in_idx, reinterpret_cast<const cplx*>(a.fbsk), a.n, a.base_log, a.num_samples, a.resid,
-                     a.guard);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("pbs launch failed: %s", hipGetErrorString(e));
-    return -1;
-  }
-  return 0;
+  return launch_fused(pbs1024_pair_slot_kernel<RESID, STAMPS>, P, P * 128, lds, a);
 }
 
 // the slot-split kernel (4 ciphertexts per workgroup, l = 3); with CONCRETE_HIP_PBS_STAMPS=1 its
@@ -927,18 +875,7 @@ static int launch_pair_t(const PbsArgs& a) {
     set_error("pbs: N=1024 l=%d logB=%u is outside the exact range", L, a.base_log);
     return -2;
   }
-  auto kern = pbs1024_pair_kernel<P, L, RESID, STAMPS>;
-  CHIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const uint32_t blocks = (a.num_samples + P - 1) / P;
-  hipLaunchKernelGGL(kern, dim3(blocks), dim3(P * 128), lds, a.stream, a.out, a.out_idx, a.luts, a.lut_idx,
-                     a.in, a.in_idx, reinterpret_cast<const cplx*>(a.fbsk), a.n, a.base_log, a.num_samples, a.resid,
-                     a.guard);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("pbs launch failed: %s", hipGetErrorString(e));
-    return -1;
-  }
-  return 0;
+  return launch_fused(pbs1024_pair_kernel<P, L, RESID, STAMPS>, P, P * 128, lds, a);
 }
 
 // compute units of the current device (cached per device)

@@ -36,6 +36,7 @@
 #include "kernel_util.hpp"
 #include "pbs.hpp"
 #include "pbs_hex.hpp"
+#include "pbs_launch.hpp"
 
 #ifndef HX_SHARED_DIGITS
 #define HX_SHARED_DIGITS 1  // rotation + decomposition shared by the three waves of a polynomial (XM)
@@ -49,38 +50,12 @@
 
 namespace chip {
 
-namespace {
+static_assert(MAGIC_ALL_3 == RND_MAGIC_BITS + (RND_MAGIC_BITS << 22) + (RND_MAGIC_BITS << 43),
+              "three limbs at shifts 0, 22, 43");
 
-constexpr uint64_t HX_MAGIC_ALL = RND_MAGIC_BITS + (RND_MAGIC_BITS << 22) + (RND_MAGIC_BITS << 43);
-constexpr int hx_limb_shift(int li) { return li * 21 + (li > 0 ? 1 : 0); }
-
-__device__ __forceinline__ void hx_signal(uint32_t* ctr, uint32_t& cnt) {
-  asm volatile("" ::: "memory");
-  ++cnt;
-  __hip_atomic_store(ctr, cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-// wait until counters ctr[0 .. NC) all reach target: the NC reads are issued together per poll
-template <int NC>
-__device__ __forceinline__ void hx_wait(const uint32_t* ctr, uint32_t target, const SyncGuard& guard) {
-  for (uint32_t it = 0;; ++it) {
-    uint32_t lo = 0xffffffffu;
-#pragma unroll
-    for (int o = 0; o < NC; ++o) {
-      const uint32_t x = __hip_atomic_load(ctr + o, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      lo = x < lo ? x : lo;
-    }
-    if (lo >= target) break;
-    if (it >= guard.spin_limit) {
-      __hip_atomic_fetch_or(guard.status, DEV_STATUS_SYNC_TIMEOUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      break;
-    }
-    __builtin_amdgcn_s_sleep(0);
-  }
-  asm volatile("" ::: "memory");
-}
-
-}  // namespace
-
+// Sync group (kernel_util.hpp): the six waves of one ciphertext signal with group_signal<6> on its
+// counters and wait with spin_until_all_ge on the counters a phase depends on (all six, the three of
+// a polynomial, or the same wave of the other ciphertext).
 template <int CTS, bool RESID, bool STAMPS = false>
 __global__ void __launch_bounds__(CTS * 384, 1)
 pbs1024_hex_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_idx,
@@ -109,15 +84,14 @@ pbs1024_hex_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_
   const bool active = s < num_samples;
   cplx* xch = xch_all + w * XS;
   uint64_t* accc = acc_all + (ctl * K1 + c) * N;
-  uint32_t* myctr = hf + ctl * 8 + u;
-  const uint32_t* ctctr = hf + ctl * 8;         // the ciphertext's six counters
+  uint32_t* ctctr = hf + ctl * 8;               // the ciphertext's six counters
   const uint32_t* polyctr = hf + ctl * 8 + 3 * c;
 
   const uint64_t* lwe = in + (active ? (in_idx ? in_idx[s] : s) : 0) * (uint64_t)(n + 1);
   const uint64_t* lut = luts + (active && lut_idx ? lut_idx[s] : 0ull) * (uint64_t)(K1 * N);
 
   build_fft512_tables(tbl, threadIdx.x, NW * 64);
-  if (lane == 0) *myctr = 0u;
+  if (lane == 0) ctctr[u] = 0u;
   // acc_c = LUT_c * X^{-ms(b)} (blind_rotate_assign: polynomial_wrapping_monic_monomial_div), stored
   // negated (pbs1024_pair_kernel): written by wave j = 0 of each polynomial
   if (j == 0) {
@@ -305,8 +279,8 @@ pbs1024_hex_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_
     if constexpr (XM) {
       pair_barrier();
     } else {
-      hx_signal(myctr, cnt);
-      hx_wait<6>(ctctr, cnt, guard);
+      group_signal<6>(ctctr, u, cnt);
+      spin_until_all_ge<6>(ctctr, cnt, guard);
     }
     lap(2);  // wait A
 
@@ -339,7 +313,7 @@ pbs1024_hex_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_
             Y[t][k].im = __builtin_fma(xv.re, gv.im, __builtin_fma(xv.im, gv.re, Y[t][k].im));
           }
         }
-      if (!XM && b == NB - 1) hx_signal(myctr, cnt);  // B: every spectrum read of this wave is issued
+      if (!XM && b == NB - 1) group_signal<6>(ctctr, u, cnt);  // B: every spectrum read of this wave is issued
       // refill: batch b + PF of this step (the next step's first PF batches are issued in the
       // inverse phase: issued here, all of a step's key loads crowded into this phase, where the
       // CU's vector-memory path — 288 KB per step — bounded it: +5.8 % without key loads, diagnostic)
@@ -364,12 +338,12 @@ pbs1024_hex_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_
         partner[k * 64] = Y[1][k];
         v[k] = Y[0][k];  // my half: natural slots 4h + k (k2 ^ 4 order for h = 1)
       }
-      hx_signal(myctr, cnt);  // M
-      hx_wait<1>(hf + (1 - ctl) * 8 + u, cnt, guard);
+      group_signal<6>(ctctr, u, cnt);  // M
+      spin_until_all_ge<1>(hf + (1 - ctl) * 8 + u, cnt, guard);
 #pragma unroll
       for (int k = 0; k < 4; ++k) v[4 + k] = xch[k * 64 + lane];  // the partner's: slots 4 (1 - h) + k
     } else {
-      hx_wait<6>(ctctr, cnt, guard);  // B
+      spin_until_all_ge<6>(ctctr, cnt, guard);  // B
 #pragma unroll
       for (int k = 0; k < 8; ++k) v[k] = Y[0][k];
     }
@@ -380,8 +354,8 @@ pbs1024_hex_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_
     for (int b = 0; b < PF; ++b) load_batch(gb[b], next_off, b);
     fft512_inv(v, xch, T, lane, hsign);
     {
-      const int lsh = j == 0 ? 0 : j == 1 ? hx_limb_shift(1) : hx_limb_shift(2);
-      const uint64_t lsub = j == 0 ? HX_MAGIC_ALL : 0ull;
+      const int lsh = j == 0 ? 0 : j == 1 ? limb_shift(1) : limb_shift(2);
+      const uint64_t lsub = j == 0 ? MAGIC_ALL_3 : 0ull;
       // limb j's exact integers, negated (B = -acc), shifted; limb 0 removes the constant of all limbs
 #pragma unroll
       for (int m = 0; m < 8; ++m) {
@@ -407,8 +381,8 @@ pbs1024_hex_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_
     if constexpr (XM) {
       pair_barrier();
     } else {
-      hx_signal(myctr, cnt);
-      hx_wait<3>(polyctr, cnt, guard);
+      group_signal<6>(ctctr, u, cnt);
+      spin_until_all_ge<3>(polyctr, cnt, guard);
     }
     lap(7);  // wait C
   }
@@ -438,27 +412,12 @@ pbs1024_hex_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_
     }
   }
 
-  if constexpr (RESID && !STAMPS) {
-    for (int off = 32; off > 0; off >>= 1) max_resid = fmax(max_resid, __shfl_xor(max_resid, off));
-    if (lane == 0 && active && resid_out) atomicMax(resid_out, (unsigned long long)__double_as_longlong(max_resid));
-  }
+  if constexpr (RESID && !STAMPS) report_resid(max_resid, lane, active, resid_out);
 }
 
 template <int CTS, bool RESID, bool STAMPS = false>
 static int launch_hex_t(const PbsArgs& a) {
-  const size_t lds = pbs1024_hex_lds_bytes(CTS);
-  auto kern = pbs1024_hex_kernel<CTS, RESID, STAMPS>;
-  CHIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const uint32_t blocks = (a.num_samples + CTS - 1) / CTS;
-  hipLaunchKernelGGL(kern, dim3(blocks), dim3(CTS * 384), lds, a.stream, a.out, a.out_idx, a.luts, a.lut_idx, a.in,
-                     a.in_idx, reinterpret_cast<const cplx*>(a.fbsk), a.n, a.base_log, a.num_samples, a.resid,
-                     a.guard);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("pbs launch failed: %s", hipGetErrorString(e));
-    return -1;
-  }
-  return 0;
+  return launch_fused(pbs1024_hex_kernel<CTS, RESID, STAMPS>, CTS, CTS * 384, pbs1024_hex_lds_bytes(CTS), a);
 }
 
 int pbs1024_hex_launch(const PbsArgs& a, int cts) {

@@ -22,42 +22,15 @@
 #include "fft512.hpp"
 #include "kernel_util.hpp"
 #include "pbs.hpp"
+#include "pbs_launch.hpp"
 
 namespace chip {
 
-namespace {
+static_assert(MAGIC_ALL_3 == RND_MAGIC_BITS + (RND_MAGIC_BITS << 22) + (RND_MAGIC_BITS << 43),
+              "three limbs at shifts 0, 22, 43");
 
-constexpr uint64_t Q_MAGIC_ALL = RND_MAGIC_BITS + (RND_MAGIC_BITS << 22) + (RND_MAGIC_BITS << 43);
-constexpr int q_limb_shift(int li) { return li * 21 + (li > 0 ? 1 : 0); }
-
-// Synchronisation of the four waves of one ciphertext (counters qf[ct * 4 + role]).
-__device__ __forceinline__ void q_sync(uint32_t* qf, int ct, int v, uint32_t& cnt, const SyncGuard& guard) {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  ++cnt;
-  __hip_atomic_store(&qf[ct * 4 + v], cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#pragma unroll
-  for (int o = 1; o < 4; ++o) spin_until_ge(&qf[ct * 4 + ((v + o) & 3)], cnt, guard);
-}
-__device__ __forceinline__ void q_signal(uint32_t* qf, int ct, int v, uint32_t& cnt) {
-  asm volatile("" ::: "memory");
-  ++cnt;
-  __hip_atomic_store(&qf[ct * 4 + v], cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-__device__ __forceinline__ void q_wait(uint32_t* qf, int ct, int v, uint32_t cnt, const SyncGuard& guard) {
-#pragma unroll
-  for (int o = 1; o < 4; ++o) spin_until_ge(&qf[ct * 4 + ((v + o) & 3)], cnt, guard);
-  asm volatile("" ::: "memory");
-}
-// the two waves of one polynomial (separate counters pf[ct * 4 + role])
-__device__ __forceinline__ void q_pair_sync(uint32_t* pf, int ct, int v, uint32_t& cnt, const SyncGuard& guard) {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  ++cnt;
-  __hip_atomic_store(&pf[ct * 4 + v], cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  spin_until_ge(&pf[ct * 4 + (v ^ 1)], cnt, guard);
-}
-
-}  // namespace
-
+// Sync groups (kernel_util.hpp): the four waves of one ciphertext (group_*<4> on its counters qf) and,
+// on separate counters pf, the two waves of one polynomial (group_sync<2> on pf + (v & 2)).
 template <int CTS, bool RESID>
 __global__ void __launch_bounds__(CTS * 256, 1)
 pbs1024_quad_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_idx,
@@ -79,14 +52,16 @@ pbs1024_quad_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
   cplx* tbl = reinterpret_cast<cplx*>(smem);
   cplx* xch_all = tbl + FFT512_TABLE_ENTRIES;  // NW scratches (transposes, spectra, mailboxes, deltas)
   cplx* ring = xch_all + NW * XS;              // 3 x GROUP key ring
-  uint32_t* qf = reinterpret_cast<uint32_t*>(ring + 3 * GROUP);  // NW quad-sync counters
-  uint32_t* pf = qf + NW;                                         // NW pair-sync counters
+  uint32_t* qflags = reinterpret_cast<uint32_t*>(ring + 3 * GROUP);  // NW quad-sync counters
+  uint32_t* pflags = qflags + NW;                                     // NW pair-sync counters
 
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   const int ctl = w >> 2;
   const int v = (w & 3) ^ (ctl & 1);  // role (ciphertext 1: h flipped, see the header)
   const int c = v >> 1, h = v & 1;
+  uint32_t* qf = qflags + ctl * 4;    // this ciphertext's counters, indexed by role
+  uint32_t* pf = pflags + ctl * 4;
   const uint32_t s = blockIdx.x * CTS + ctl;
   const bool active = s < num_samples;
   auto scr = [&](int role) __attribute__((always_inline)) {
@@ -100,17 +75,7 @@ pbs1024_quad_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
   cplx* ring_w = ring + w * GLDS * 64;
   const uint32_t lane_b = (uint32_t)lane * (uint32_t)sizeof(cplx);
   auto issue_group = [&](const cplx* key_step, int r) __attribute__((always_inline)) {
-    const char* src = reinterpret_cast<const char*>(key_step + r * GROUP);
-    cplx* dst = ring_w + (r % 3) * GROUP;
-#pragma unroll
-    for (int j = 0; j < GLDS; ++j) {
-      const cplx* gp = reinterpret_cast<const cplx*>(src + j * 1024 + lane_b);
-      const uint32_t m0 = (uint32_t)(uintptr_t)(lds_ptr_t)(dst + j * 64);
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-      asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dwordx4 %0, off" : : "v"(gp), "s"(m0) : "m0", "memory");
-#pragma clang diagnostic pop
-    }
+    ring_issue<GLDS, true>(reinterpret_cast<const char*>(key_step + r * GROUP), ring_w + (r % 3) * GROUP, lane_b);
   };
   if (n > 0) {
     issue_group(key_w, 0);
@@ -118,7 +83,7 @@ pbs1024_quad_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
   }
 
   build_fft512_tables(tbl, threadIdx.x, NW * 64);
-  if (lane == 0) qf[w] = 0u, pf[w] = 0u;
+  if (lane == 0) qflags[w] = 0u, pflags[w] = 0u;
   uint32_t qcnt = 0, pcnt = 0;
   __syncthreads();
   const Fft512Tables T = fft512_tables_at(tbl);
@@ -156,11 +121,11 @@ pbs1024_quad_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
         max_resid = fmax(max_resid, fabs(vv[m].im - (RND_MAGIC - ti)));
       }
       if constexpr (lr == 0) {
-        D[m] += (uint64_t)__double_as_longlong(tr) - Q_MAGIC_ALL;
-        D[m + 8] += (uint64_t)__double_as_longlong(ti) - Q_MAGIC_ALL;
+        D[m] += (uint64_t)__double_as_longlong(tr) - MAGIC_ALL_3;
+        D[m + 8] += (uint64_t)__double_as_longlong(ti) - MAGIC_ALL_3;
       } else {
-        D[m] += (uint64_t)__double_as_longlong(tr) << q_limb_shift(lr);
-        D[m + 8] += (uint64_t)__double_as_longlong(ti) << q_limb_shift(lr);
+        D[m] += (uint64_t)__double_as_longlong(tr) << limb_shift(lr);
+        D[m + 8] += (uint64_t)__double_as_longlong(ti) << limb_shift(lr);
       }
     }
   };
@@ -228,7 +193,7 @@ pbs1024_quad_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
 #pragma unroll
       for (int k2 = 0; k2 < 8; ++k2) xch[k2 * 64 + lane] = vv[k2];
     }
-    q_sync(qf, ctl, v, qcnt, guard);
+    group_sync<4>(qf, v, qcnt, guard);
 #pragma unroll
     for (int r = 0; r < K1; ++r) {
       const int p = r ^ c;
@@ -242,13 +207,13 @@ pbs1024_quad_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
     for (int r = 0; r < K1; ++r)
 #pragma unroll
       for (int jj = 0; jj < 2; ++jj) pin(X[r][0][jj]), pin(X[r][2][jj]);
-    q_signal(qf, ctl, v, qcnt);
+    group_signal<4>(qf, v, qcnt);
     if (h == 0) {  // F2: level 1, published by the first key window's barrier
       cplx vv[8];
 #pragma unroll
       for (int m = 0; m < 8; ++m) vv[m] = {(double)dB[m], (double)dB[m + 8]};
       fft512_fwd_tw(vv, xch, lane, tw2, tw3, 0, [&]() __attribute__((always_inline)) {
-        q_wait(qf, ctl, v, qcnt, guard);  // my F1 spectrum has been read
+        group_wait<4>(qf, v, qcnt, guard);  // my F1 spectrum has been read
       });
 #pragma unroll
       for (int k2 = 0; k2 < 8; ++k2) xch[k2 * 64 + lane] = vv[k2];
@@ -318,7 +283,7 @@ pbs1024_quad_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
     }
 #pragma unroll
     for (int m = 0; m < 16; ++m) D[m] = 0ull;
-    q_sync(qf, ctl, v, qcnt, guard);  // S1: mailboxes of limbs 0 and 1 complete
+    group_sync<4>(qf, v, qcnt, guard);  // S1: mailboxes of limbs 0 and 1 complete
     {  // IA: limb h of my polynomial
       cplx vv[8];
 #pragma unroll
@@ -331,7 +296,7 @@ pbs1024_quad_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
 #pragma unroll
       for (int m = 0; m < 16; ++m) xch64[lane + 64 * m] = D[m];
     }
-    q_sync(qf, ctl, v, qcnt, guard);  // S2: IA done everywhere; h = 0 deltas written
+    group_sync<4>(qf, v, qcnt, guard);  // S2: IA done everywhere; h = 0 deltas written
     uint64_t Dsib[16];
     if (h == 1) {
       const uint64_t* sib = reinterpret_cast<const uint64_t*>(scr(2 * c));
@@ -344,7 +309,7 @@ pbs1024_quad_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
 #pragma unroll
       for (int jj = 0; jj < 2; ++jj) scr(2 * C + 1)[(2 * v + jj) * 64 + lane] = Y[2][co][jj];
     }
-    q_sync(qf, ctl, v, qcnt, guard);  // S3: mailboxes of limb 2 complete (h = 1 scratches)
+    group_sync<4>(qf, v, qcnt, guard);  // S3: mailboxes of limb 2 complete (h = 1 scratches)
     if (h == 1) {  // IB: limb 2; then my delta (limbs 1 + 2) into my sibling's scratch
       cplx vv[8];
 #pragma unroll
@@ -355,7 +320,7 @@ pbs1024_quad_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
 #pragma unroll
       for (int m = 0; m < 16; ++m) sib[lane + 64 * m] = D[m];
     }
-    q_pair_sync(pf, ctl, v, pcnt, guard);  // P1: the h = 1 delta is in the h = 0 scratch
+    group_sync<2>(pf + (v & 2), h, pcnt, guard);  // P1: the h = 1 delta is in the h = 0 scratch
     if (h == 0) {
 #pragma unroll
       for (int m = 0; m < 16; ++m) Dsib[m] = xch64[lane + 64 * m];
@@ -385,27 +350,12 @@ pbs1024_quad_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
     o[K * N] = 0ull - B[0];
   }
 
-  if constexpr (RESID) {
-    for (int off = 32; off > 0; off >>= 1) max_resid = fmax(max_resid, __shfl_xor(max_resid, off));
-    if (lane == 0 && active && resid_out) atomicMax(resid_out, (unsigned long long)__double_as_longlong(max_resid));
-  }
+  if constexpr (RESID) report_resid(max_resid, lane, active, resid_out);
 }
 
 template <int CTS, bool RESID>
 static int launch_quad_t(const PbsArgs& a) {
-  const size_t lds = pbs1024_quad_lds_bytes(CTS);
-  auto kern = pbs1024_quad_kernel<CTS, RESID>;
-  CHIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const uint32_t blocks = (a.num_samples + CTS - 1) / CTS;
-  hipLaunchKernelGGL(kern, dim3(blocks), dim3(CTS * 256), lds, a.stream, a.out, a.out_idx, a.luts, a.lut_idx, a.in,
-                     a.in_idx, reinterpret_cast<const cplx*>(a.fbsk), a.n, a.base_log, a.num_samples, a.resid,
-                     a.guard);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("pbs launch failed: %s", hipGetErrorString(e));
-    return -1;
-  }
-  return 0;
+  return launch_fused(pbs1024_quad_kernel<CTS, RESID>, CTS, CTS * 256, pbs1024_quad_lds_bytes(CTS), a);
 }
 
 int pbs1024_quad_launch(const PbsArgs& a, int cts) {

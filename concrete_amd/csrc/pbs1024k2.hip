@@ -31,6 +31,7 @@
 #include "fft512.hpp"
 #include "kernel_util.hpp"
 #include "pbs.hpp"
+#include "pbs_launch.hpp"
 
 #include <type_traits>
 
@@ -38,8 +39,9 @@ namespace chip {
 
 namespace {
 
-constexpr uint64_t K2_MAGIC_ALL =
-    RND_MAGIC_BITS + (RND_MAGIC_BITS << 16) + (RND_MAGIC_BITS << 32) + (RND_MAGIC_BITS << 48);
+static_assert(limb_magic_all(4, 16) ==
+                  RND_MAGIC_BITS + (RND_MAGIC_BITS << 16) + (RND_MAGIC_BITS << 32) + (RND_MAGIC_BITS << 48),
+              "four 16-bit limbs");
 
 // first frequency slot of wave v's share (v = 0, 1, 2; SB(3) = 8)
 #ifndef K2_SB1
@@ -77,44 +79,14 @@ constexpr uint64_t K2_MAGIC_ALL =
 #endif
 __device__ __forceinline__ int k2_slot_base(int v) { return v == 0 ? 0 : (v == 1 ? K2_SB1 : K2_SB2); }
 
-// Synchronisation of the three waves of one ciphertext (never the other ciphertext of the
-// workgroup): each wave publishes how many sync points it has passed and waits until its two
-// partners have reached the same count.  LDS traffic is drained, the key DMA is not.
-__device__ __forceinline__ void tri_sync(uint32_t* flags, int ctl, int v, uint32_t& cnt, const SyncGuard& guard) {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  if (K2D_NOTRI) return;
-  ++cnt;
-  __hip_atomic_store(&flags[ctl * 3 + v], cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  spin_until_ge(&flags[ctl * 3 + (v == 2 ? 0 : v + 1)], cnt, guard);
-  spin_until_ge(&flags[ctl * 3 + (v == 0 ? 2 : v - 1)], cnt, guard);
+// Sync group (kernel_util.hpp group_*<3>): the three waves of one ciphertext, tf = its counters; in
+// the many-level kernel the four waves of one ciphertext (group_*<4>, counter index = role).
+__device__ __forceinline__ void tri_sync(uint32_t* tf, int v, uint32_t& cnt, const SyncGuard& guard) {
+  if constexpr (K2D_NOTRI) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  else group_sync<3>(tf, v, cnt, guard);
 }
-// Split form: tri_signal publishes that this wave's reads of its partners' scratches have been
-// issued (LDS operations of a wave execute in order); tri_wait, before this wave next overwrites
-// its own scratch, waits for its partners' signals.
-__device__ __forceinline__ void tri_signal(uint32_t* flags, int ctl, int v, uint32_t& cnt) {
-  asm volatile("" ::: "memory");
-  ++cnt;
-  __hip_atomic_store(&flags[ctl * 3 + v], cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-__device__ __forceinline__ void tri_wait(uint32_t* flags, int ctl, int v, uint32_t cnt, const SyncGuard& guard) {
-  if (K2D_NOTRI) return;
-  spin_until_ge(&flags[ctl * 3 + (v == 2 ? 0 : v + 1)], cnt, guard);
-  spin_until_ge(&flags[ctl * 3 + (v == 0 ? 2 : v - 1)], cnt, guard);
-  asm volatile("" ::: "memory");
-}
-
-// the four waves of one ciphertext in the many-level kernel (counters f[ct * 4 + role])
-__device__ __forceinline__ void k2q_signal(uint32_t* f, int ctl, int role, uint32_t& cnt) {
-  asm volatile("" ::: "memory");
-  ++cnt;
-  __hip_atomic_store(&f[ctl * 4 + role], cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-__device__ __forceinline__ void k2q_sync(uint32_t* f, int ctl, int role, uint32_t& cnt, const SyncGuard& guard) {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  k2q_signal(f, ctl, role, cnt);
-#pragma unroll
-  for (int o = 1; o < 4; ++o) spin_until_ge(&f[ctl * 4 + ((role + o) & 3)], cnt, guard);
-  asm volatile("" ::: "memory");
+__device__ __forceinline__ void tri_wait(const uint32_t* tf, int v, uint32_t cnt, const SyncGuard& guard) {
+  if constexpr (!K2D_NOTRI) group_wait<3>(tf, v, cnt, guard);
 }
 
 }  // namespace
@@ -155,6 +127,7 @@ pbs1024k2_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_id
   const int lane = threadIdx.x & 63;
   const int ctl = w / 3;  // ciphertext within the workgroup
   const int v = w - 3 * ctl;  // own polynomial
+  uint32_t* tf = tflags + ctl * 3;  // this ciphertext's three counters
   const int sb = k2_slot_base(v);
   // slots of my share; every share has at least 2 (K2_SB1, K2_SB2), so only slot 2 is conditional
   const int ns = (v == 2 ? 8 : k2_slot_base(v + 1)) - sb;
@@ -174,22 +147,8 @@ pbs1024k2_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_id
   cplx* ring_w = ring + w * GLDS * 64;
   const uint32_t lane_b = (uint32_t)lane * (uint32_t)sizeof(cplx);
   auto issue_group = [&](const cplx* key_step, int r) __attribute__((always_inline)) {
-    const char* src = reinterpret_cast<const char*>(key_step + r * GROUP);
-    cplx* dst = ring_w + (r % RS) * GROUP;
-#pragma unroll
-    for (int j = 0; j < GLDS; ++j) {
-#if K2_ASM_DMA
-      const cplx* gp = reinterpret_cast<const cplx*>(src + j * 1024 + lane_b);
-      const uint32_t m0 = (uint32_t)(uintptr_t)(lds_ptr_t)(dst + j * 64);
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-      asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dwordx4 %0, off" : : "v"(gp), "s"(m0) : "m0", "memory");
-#pragma clang diagnostic pop
-#else
-      __builtin_amdgcn_global_load_lds(reinterpret_cast<const cplx*>(src + j * 1024 + lane_b),
-                                       (lds_ptr_t)(dst + j * 64), 16, 0, 0);
-#endif
-    }
+    ring_issue<GLDS, K2_ASM_DMA != 0>(reinterpret_cast<const char*>(key_step + r * GROUP), ring_w + (r % RS) * GROUP,
+                                      lane_b);
   };
   if (n > 0) {
 #pragma unroll
@@ -283,7 +242,7 @@ pbs1024k2_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_id
         // transform's first LDS write (the partners signalled right after their reads)
         if (!K2D_NOFWD)
           fft512_fwd_tw(vv8, xch, lane, tw2, tw3, 0, [&]() __attribute__((always_inline)) {
-            if (sub > 0) tri_wait(tflags, ctl, v, tcnt, guard);
+            if (sub > 0) tri_wait(tf, v, tcnt, guard);
           });
 #pragma unroll
         for (int k2 = 0; k2 < 8; ++k2) xch[k2 * 64 + lane] = vv8[k2];
@@ -291,7 +250,7 @@ pbs1024k2_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_id
       // The last sub-digit's spectra need no sync: the first key window's workgroup barrier
       // (which drains every wave's LDS writes) publishes them; they are read right after it.
       if (sub + 1 < NF) {
-        tri_sync(tflags, ctl, v, tcnt, guard);
+        tri_sync(tf, v, tcnt, guard);
 #pragma unroll
         for (int row = 0; row < K1; ++row)
 #pragma unroll
@@ -301,7 +260,7 @@ pbs1024k2_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_id
         for (int row = 0; row < K1; ++row)
 #pragma unroll
           for (int jj = 0; jj < MS; ++jj) pin(X[row][sub][jj]);
-        tri_signal(tflags, ctl, v, tcnt);
+        group_signal<3>(tf, v, tcnt);
       }
     }
 
@@ -433,7 +392,7 @@ pbs1024k2_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_id
         }
       }
       cplx V[8];
-      tri_sync(tflags, ctl, v, tcnt, guard);
+      tri_sync(tf, v, tcnt, guard);
 #pragma unroll
       for (int k2 = 0; k2 < 8; ++k2) V[k2] = xch[k2 * 64 + lane];
       {
@@ -449,8 +408,8 @@ pbs1024k2_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_id
           max_resid = fmax(max_resid, fabs(V[m].im - (ti - RND_MAGIC)));
         }
         if constexpr (li == 0) {
-          A[m] += (uint64_t)__double_as_longlong(tr) - K2_MAGIC_ALL;
-          A[m + 8] += (uint64_t)__double_as_longlong(ti) - K2_MAGIC_ALL;
+          A[m] += (uint64_t)__double_as_longlong(tr) - limb_magic_all(K2_LIMBS, 16);
+          A[m + 8] += (uint64_t)__double_as_longlong(ti) - limb_magic_all(K2_LIMBS, 16);
         } else {
           A[m] += (uint64_t)__double_as_longlong(tr) << (16 * li);
           A[m + 8] += (uint64_t)__double_as_longlong(ti) << (16 * li);
@@ -481,27 +440,12 @@ pbs1024k2_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_id
     o[2 * N] = A[0];
   }
 
-  if constexpr (RESID) {
-    for (int off = 32; off > 0; off >>= 1) max_resid = fmax(max_resid, __shfl_xor(max_resid, off));
-    if (lane == 0 && active && resid_out) atomicMax(resid_out, (unsigned long long)__double_as_longlong(max_resid));
-  }
+  if constexpr (RESID) report_resid(max_resid, lane, active, resid_out);
 }
 
 template <bool RESID, int NQ>
 static int launch_k2_t(const PbsArgs& a) {
-  const size_t lds = pbs1024k2_lds_bytes();
-  auto kern = pbs1024k2_kernel<RESID, NQ>;
-  CHIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const uint32_t blocks = (a.num_samples + K2_CTS - 1) / K2_CTS;
-  hipLaunchKernelGGL(kern, dim3(blocks), dim3(K2_CTS * 192), lds, a.stream, a.out, a.out_idx, a.luts, a.lut_idx,
-                     a.in, a.in_idx, reinterpret_cast<const cplx*>(a.fbsk), a.n, a.base_log, a.num_samples, a.resid,
-                     a.guard);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("pbs launch failed: %s", hipGetErrorString(e));
-    return -1;
-  }
-  return 0;
+  return launch_fused(pbs1024k2_kernel<RESID, NQ>, K2_CTS, K2_CTS * 192, pbs1024k2_lds_bytes(), a);
 }
 
 // Many levels (l >= K2_MANY_MIN, runtime), whole digits, one level at a time (as
@@ -539,6 +483,7 @@ pbs1024k2_many_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ o
   const int role = ctl == 0 ? (w & 3) : ((w + 1) & 3);  // slots 2 role, 2 role + 1
   const bool owner = role < 3;
   const int v = owner ? role : 0;           // owned polynomial
+  uint32_t* tf = tflags + ctl * 4;          // this ciphertext's four counters
   const uint32_t s = blockIdx.x * K2_CTS + ctl;
   const bool active = s < num_samples;
   cplx* ctx = xch_all + ctl * 3 * XS;
@@ -552,12 +497,8 @@ pbs1024k2_many_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ o
   const uint32_t lane_b = (uint32_t)lane * (uint32_t)sizeof(cplx);
   auto issue_group = [&](const cplx* key_step, uint32_t g) __attribute__((always_inline)) {
     if (!issuer) return;
-    const char* src = reinterpret_cast<const char*>(key_step + (uint64_t)g * GROUP);
-    cplx* dst = ring_w + (g % RS) * GROUP;
-#pragma unroll
-    for (int j = 0; j < GLDS; ++j)
-      __builtin_amdgcn_global_load_lds(reinterpret_cast<const cplx*>(src + j * 1024 + lane_b),
-                                       (lds_ptr_t)(dst + j * 64), 16, 0, 0);
+    ring_issue<GLDS, false>(reinterpret_cast<const char*>(key_step + (uint64_t)g * GROUP),
+                            ring_w + (g % RS) * GROUP, lane_b);
   };
   if (n > 0) {
 #pragma unroll
@@ -685,7 +626,7 @@ pbs1024k2_many_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ o
 #pragma unroll
         for (int jj = 0; jj < MS; ++jj) myslot[cc * XS + jj * 64] = Y[li][cc][jj];
       if (owner) {
-        k2q_sync(tflags, ctl, role, tcnt, guard);
+        group_sync_composed<4>(tf, role, tcnt, guard);
         cplx V[8];
 #pragma unroll
         for (int k2 = 0; k2 < 8; ++k2) V[k2] = xch[k2 * 64 + lane];
@@ -702,8 +643,8 @@ pbs1024k2_many_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ o
             max_resid = fmax(max_resid, fabs(V[m].im - (ti - RND_MAGIC)));
           }
           if (li == 0) {
-            A[m] += (uint64_t)__double_as_longlong(tr) - K2_MAGIC_ALL;
-            A[m + 8] += (uint64_t)__double_as_longlong(ti) - K2_MAGIC_ALL;
+            A[m] += (uint64_t)__double_as_longlong(tr) - limb_magic_all(K2_LIMBS, 16);
+            A[m + 8] += (uint64_t)__double_as_longlong(ti) - limb_magic_all(K2_LIMBS, 16);
           } else {
             A[m] += (uint64_t)__double_as_longlong(tr) << (16 * li);
             A[m + 8] += (uint64_t)__double_as_longlong(ti) << (16 * li);
@@ -713,7 +654,7 @@ pbs1024k2_many_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ o
         for (int m = 0; m < 16; ++m) pin(A[m]);
       } else {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        k2q_signal(tflags, ctl, role, tcnt);
+        group_signal<4>(tf, role, tcnt);
       }
       pair_barrier();  // every owner is done with its scratch
     }
@@ -735,27 +676,12 @@ pbs1024k2_many_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ o
     o[2 * N] = A[0];
   }
 
-  if constexpr (RESID) {
-    for (int off = 32; off > 0; off >>= 1) max_resid = fmax(max_resid, __shfl_xor(max_resid, off));
-    if (lane == 0 && active && resid_out) atomicMax(resid_out, (unsigned long long)__double_as_longlong(max_resid));
-  }
+  if constexpr (RESID) report_resid(max_resid, lane, active, resid_out);
 }
 
 template <bool RESID>
 static int launch_k2_many_t(const PbsArgs& a) {
-  const size_t lds = pbs1024k2_many_lds_bytes();
-  auto kern = pbs1024k2_many_kernel<RESID>;
-  CHIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const uint32_t blocks = (a.num_samples + K2_CTS - 1) / K2_CTS;
-  hipLaunchKernelGGL(kern, dim3(blocks), dim3(K2_CTS * 256), lds, a.stream, a.out, a.out_idx, a.luts, a.lut_idx,
-                     a.in, a.in_idx, reinterpret_cast<const cplx*>(a.fbsk), a.n, a.level, a.base_log,
-                     a.num_samples, a.resid, a.guard);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("pbs launch failed: %s", hipGetErrorString(e));
-    return -1;
-  }
-  return 0;
+  return launch_fused(pbs1024k2_many_kernel<RESID>, K2_CTS, K2_CTS * 256, pbs1024k2_many_lds_bytes(), a);
 }
 
 int pbs1024k2_launch(const PbsArgs& a) {

@@ -37,28 +37,15 @@
 #include "fft512.hpp"
 #include "kernel_util.hpp"
 #include "pbs.hpp"
+#include "pbs_launch.hpp"
 
 #include <type_traits>
 
 namespace chip {
 
-constexpr uint64_t P2_MAGIC_ALL =
-    RND_MAGIC_BITS + (RND_MAGIC_BITS << 16) + (RND_MAGIC_BITS << 32) + (RND_MAGIC_BITS << 48);
-
-// Synchronisation of the four waves of one ciphertext (the exchanges never involve the other
-// ciphertext of the workgroup): each wave publishes how many sync points it has passed and
-// waits until its three partners have reached the same count.  LDS traffic is drained, the
-// key DMA is not.
-__device__ __forceinline__ void quad_sync(uint32_t* flags, int ctl, int v, uint32_t& cnt, const SyncGuard& guard) {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#if defined(D4_NOQS) && D4_NOQS
-  return;
-#endif
-  ++cnt;
-  __hip_atomic_store(&flags[ctl * 4 + v], cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#pragma unroll
-  for (int o = 1; o < 4; ++o) spin_until_ge(&flags[ctl * 4 + ((v + o) & 3)], cnt, guard);
-}
+static_assert(limb_magic_all(4, 16) ==
+                  RND_MAGIC_BITS + (RND_MAGIC_BITS << 16) + (RND_MAGIC_BITS << 32) + (RND_MAGIC_BITS << 48),
+              "four 16-bit limbs");
 
 // Diagnostic builds only (timing, wrong results): D4_NOBAR (no key-window barriers), D4_NOMAC
 // (no key MAC FMAs), D4_NOINV (no inverse transforms), D4_NOFWD (no forward transforms),
@@ -85,26 +72,11 @@ __device__ __forceinline__ void quad_sync(uint32_t* flags, int ctl, int v, uint3
 #ifndef P2_SPLIT_XSYNC
 #define P2_SPLIT_XSYNC 1  // split second sync of the sub-0 exchange (+1.1 %)
 #endif
-// Split form of quad_sync: quad_signal publishes that this wave's reads of the partners'
-// scratches have been issued (LDS operations of a wave execute in order, so the count is seen
-// after them); quad_wait, before this wave next overwrites its scratch, waits for the partners.
-__device__ __forceinline__ void quad_signal(uint32_t* flags, int ctl, int v, uint32_t& cnt) {
-  asm volatile("" ::: "memory");
-  ++cnt;
-  __hip_atomic_store(&flags[ctl * 4 + v], cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-__device__ __forceinline__ void quad_wait(uint32_t* flags, int ctl, int v, uint32_t cnt, const SyncGuard& guard) {
-#pragma unroll
-  for (int o = 1; o < 4; ++o) spin_until_ge(&flags[ctl * 4 + ((v + o) & 3)], cnt, guard);
-  asm volatile("" ::: "memory");
-}
-
-// The same counters for the two parity waves of one polynomial (v, v ^ 1) only.
-__device__ __forceinline__ void pair_sync2048(uint32_t* flags, int ctl, int v, uint32_t& cnt, const SyncGuard& guard) {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  ++cnt;
-  __hip_atomic_store(&flags[ctl * 4 + v], cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  spin_until_ge(&flags[ctl * 4 + (v ^ 1)], cnt, guard);
+// Sync group (kernel_util.hpp group_*<4>): the four waves of one ciphertext, qf = its counters;
+// group_sync<2> on qf + (v & 2) joins the two parity waves of one polynomial only.
+__device__ __forceinline__ void quad_sync(uint32_t* qf, int v, uint32_t& cnt, const SyncGuard& guard) {
+  if constexpr (D4_NOQS) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  else group_sync<4>(qf, v, cnt, guard);
 }
 
 // NQ = 1: one digit split into d_lo + 2^16 d_hi (logB <= 24); NQ = l = 2 .. 4: whole digits
@@ -140,6 +112,7 @@ pbs2048_quad_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
   const int ctl = w >> 2;            // ciphertext within the workgroup
   const int v = w & 3;               // virtual polynomial = frequency quarter
   const int c = v >> 1, par = v & 1;
+  uint32_t* qf = qflags + ctl * 4;   // this ciphertext's four counters
   const uint32_t s = blockIdx.x * PBS2_CTS + ctl;
   const bool active = s < num_samples;
   cplx* xch = xch_all + w * XS;
@@ -155,12 +128,7 @@ pbs2048_quad_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
   cplx* ring_w = ring + w * GLDS * 64;
   const uint32_t lane_b = (uint32_t)lane * (uint32_t)sizeof(cplx);  // zero-extended lane offset
   auto issue_group = [&](const cplx* key_step, int r) __attribute__((always_inline)) {
-    const char* src = reinterpret_cast<const char*>(key_step + r * GROUP);
-    cplx* dst = ring_w + (r % RS) * GROUP;
-#pragma unroll
-    for (int j = 0; j < GLDS; ++j)
-      __builtin_amdgcn_global_load_lds(reinterpret_cast<const cplx*>(src + j * 1024 + lane_b),
-                                       (lds_ptr_t)(dst + j * 64), 16, 0, 0);
+    ring_issue<GLDS, false>(reinterpret_cast<const char*>(key_step + r * GROUP), ring_w + (r % RS) * GROUP, lane_b);
   };
   if (n > 0) {
 #pragma unroll
@@ -252,7 +220,7 @@ pbs2048_quad_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
     // next transform overwrites my scratch, which my partner reads).  `at` is the same for all
     // four waves, so the four sync counters stay equal.
     const bool odd = (at & 1u) != 0u;
-    if (odd) pair_sync2048(qflags, ctl, v, qcnt, guard);
+    if (odd) group_sync<2>(qf + (v & 2), par, qcnt, guard);
     else wave_lds_fence();
     {
 #pragma unroll
@@ -264,7 +232,7 @@ pbs2048_quad_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
         st[m] = (StT)decomp_init((sp < N ? rv : 0ull - rv) - A[m], nrep);
       }
     }
-    if (odd) pair_sync2048(qflags, ctl, v, qcnt, guard);  // my partner has read my scratch
+    if (odd) group_sync<2>(qf + (v & 2), par, qcnt, guard);  // my partner has read my scratch
 
     // ---- digit polynomials (two sub-digits of one level, or NQ levels), forward transforms --
     // X[vv][f][jj]: spectrum of digit polynomial f (virtual poly vv = 2 row + parity) at
@@ -299,7 +267,7 @@ pbs2048_quad_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
           // the sub-0 exchange's "everyone has read my spectrum" wait, right before this
           // transform's first LDS write (the partners signalled right after their reads)
           fft512_fwd_tw(vv8, xch, lane, tw2, tw3, 0, [&]() __attribute__((always_inline)) {
-            if (sub > 0) quad_wait(qflags, ctl, v, qcnt, guard);
+            if (sub > 0) group_wait<4>(qf, v, qcnt, guard);
           });
         }
 #else
@@ -312,7 +280,7 @@ pbs2048_quad_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
       // (which drains every wave's LDS writes) publishes them, and they are first used in the
       // second window (sub 1); they are read right after that barrier.
       if (sub + 1 < NF) {
-        quad_sync(qflags, ctl, v, qcnt, guard);
+        quad_sync(qf, v, qcnt, guard);
 #pragma unroll
         for (int vv = 0; vv < 4; ++vv)
 #pragma unroll
@@ -328,9 +296,9 @@ pbs2048_quad_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
       // everyone has read my spectrum before my next transform writes the scratch; after the
       // last sub-digit the scratches are next written behind the key windows' barriers
 #if P2_SPLIT_XSYNC
-      if (sub + 1 < NF) quad_signal(qflags, ctl, v, qcnt);
+      if (sub + 1 < NF) group_signal<4>(qf, v, qcnt);
 #else
-      if (sub + 1 < NF) quad_sync(qflags, ctl, v, qcnt, guard);
+      if (sub + 1 < NF) quad_sync(qf, v, qcnt, guard);
 #endif
     }
 
@@ -366,8 +334,8 @@ pbs2048_quad_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
           max_resid = fmax(max_resid, fabs(V[m].im - (ti - RND_MAGIC)));
         }
         if constexpr (lj == 0) {
-          A[m] += (uint64_t)__double_as_longlong(tr) - P2_MAGIC_ALL;
-          A[m + 8] += (uint64_t)__double_as_longlong(ti) - P2_MAGIC_ALL;
+          A[m] += (uint64_t)__double_as_longlong(tr) - limb_magic_all(PBS2_LIMBS, 16);
+          A[m + 8] += (uint64_t)__double_as_longlong(ti) - limb_magic_all(PBS2_LIMBS, 16);
         } else {
           A[m] += (uint64_t)__double_as_longlong(tr) << (16 * lj);
           A[m + 8] += (uint64_t)__double_as_longlong(ti) << (16 * lj);
@@ -509,7 +477,7 @@ pbs2048_quad_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
       // others after the next limb's first key-window barrier (P2_DEFER_INV), which publishes the
       // mailboxes as this quad sync does
       if constexpr (!P2_DEFER_INV || li + 1 == PBS2_LIMBS) {
-        quad_sync(qflags, ctl, v, qcnt, guard);
+        quad_sync(qf, v, qcnt, guard);
         inverse_limb(LI);
       }
     });
@@ -535,27 +503,12 @@ pbs2048_quad_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
     o[N] = A[0];
   }
 
-  if constexpr (RESID) {
-    for (int off = 32; off > 0; off >>= 1) max_resid = fmax(max_resid, __shfl_xor(max_resid, off));
-    if (lane == 0 && active && resid_out) atomicMax(resid_out, (unsigned long long)__double_as_longlong(max_resid));
-  }
+  if constexpr (RESID) report_resid(max_resid, lane, active, resid_out);
 }
 
 template <bool RESID, int NQ>
 static int launch2048_t(const PbsArgs& a) {
-  const size_t lds = pbs2048_lds_bytes();
-  auto kern = pbs2048_quad_kernel<RESID, NQ>;
-  CHIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const uint32_t blocks = (a.num_samples + PBS2_CTS - 1) / PBS2_CTS;
-  hipLaunchKernelGGL(kern, dim3(blocks), dim3(PBS2_CTS * 256), lds, a.stream, a.out, a.out_idx, a.luts, a.lut_idx,
-                     a.in, a.in_idx, reinterpret_cast<const cplx*>(a.fbsk), a.n, a.base_log, a.num_samples, a.resid,
-                     a.guard);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("pbs launch failed: %s", hipGetErrorString(e));
-    return -1;
-  }
-  return 0;
+  return launch_fused(pbs2048_quad_kernel<RESID, NQ>, PBS2_CTS, PBS2_CTS * 256, pbs2048_lds_bytes(), a);
 }
 
 int pbs2048_launch(const PbsArgs& a) {

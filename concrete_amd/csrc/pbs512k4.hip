@@ -22,40 +22,18 @@
 #include "fft512.hpp"
 #include "kernel_util.hpp"
 #include "pbs.hpp"
+#include "pbs_launch.hpp"
 
 #include <type_traits>
 
 namespace chip {
 
-namespace {
+static_assert(limb_magic_all(4, 16) ==
+                  RND_MAGIC_BITS + (RND_MAGIC_BITS << 16) + (RND_MAGIC_BITS << 32) + (RND_MAGIC_BITS << 48),
+              "four 16-bit limbs");
 
-// sum over the key limbs of the rounding constant at each limb's shift (LB bits per limb)
-constexpr uint64_t k4_magic_all(int limbs, int lb) {
-  uint64_t m = 0;
-  for (int li = 0; li < limbs; ++li) m += RND_MAGIC_BITS << (lb * li);
-  return m;
-}
-
-// the four waves of one ciphertext (counters f[ct * 4 + role]): publish how many sync points this
-// wave has passed; wait until the other three have reached a count.  LDS traffic is drained, the key
-// DMA is not.
-__device__ __forceinline__ void k4_signal(uint32_t* f, int ctl, int role, uint32_t& cnt) {
-  asm volatile("" ::: "memory");
-  ++cnt;
-  __hip_atomic_store(&f[ctl * 4 + role], cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-__device__ __forceinline__ void k4_wait(uint32_t* f, int ctl, int role, uint32_t cnt, const SyncGuard& guard) {
-#pragma unroll
-  for (int o = 1; o < 4; ++o) spin_until_ge(&f[ctl * 4 + ((role + o) & 3)], cnt, guard);
-  asm volatile("" ::: "memory");
-}
-__device__ __forceinline__ void k4_sync(uint32_t* f, int ctl, int role, uint32_t& cnt, const SyncGuard& guard) {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  k4_signal(f, ctl, role, cnt);
-  k4_wait(f, ctl, role, cnt, guard);
-}
-
-}  // namespace
+// Sync group (kernel_util.hpp group_*<4>, the composed sync): the four waves of one ciphertext,
+// tf = its counters, counter index = role.
 
 // SUBS = 2, NQ = 1: one digit split into d_lo + 2^16 d_hi (16 < logB <= 24); SUBS = 1: NQ = l whole
 // digits, each level's products landing in the same slot (the key holds the levels,
@@ -77,7 +55,7 @@ pbs512k4_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_idx
   constexpr int GROUP = K1 * M;             // (limb, column): the five row spectra
   constexpr int LB = LIMBS == 4 ? 16 : 13;  // limb grid: limb li at 2^{LB li} (the last of 5: 12 bits)
   static_assert(LIMBS == 4 || (LIMBS == 5 && SUBS == 1), "sub-digits need the 16-bit grid");
-  constexpr uint64_t MAGIC_ALL = k4_magic_all(LIMBS, LB);
+  constexpr uint64_t MAGIC_ALL = limb_magic_all(LIMBS, LB);
   constexpr int NGRP = LIMBS * K1 * NQ;     // ring groups per CMUX step
   constexpr int NF = SUBS * NQ;             // forward transforms per step (sub-digits or levels)
   static_assert(SUBS == 1 || NQ == 1, "sub-digits or levels");
@@ -102,6 +80,7 @@ pbs512k4_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_idx
   const int ctl = w >> 2;
   const int role = ctl == 0 ? (w & 3) : ((w + 1) & 3);  // = my key-product slot
   const bool owner = role < 3;
+  uint32_t* tf = tflags + ctl * 4;          // this ciphertext's four counters
   const int v = owner ? role : 0;           // owned pair (role 3: none)
   const int pl = lane & 1;                  // my lane's polynomial within the pair
   const int pa = 2 * v + pl;                // ... absolute (5: the empty half of role 2)
@@ -124,12 +103,8 @@ pbs512k4_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_idx
   };
   auto issue_group = [&](const cplx* key_step, uint32_t i, int r) __attribute__((always_inline)) {
     if (!issuer) return;
-    const char* src = reinterpret_cast<const char*>(key_step + r * GROUP);
-    cplx* dst = ring_w + slot_of(i, r) * GROUP;
-#pragma unroll
-    for (int j = 0; j < GLDS; ++j)
-      __builtin_amdgcn_global_load_lds(reinterpret_cast<const cplx*>(src + j * 1024 + lane_b),
-                                       (lds_ptr_t)(dst + j * 64), 16, 0, 0);
+    ring_issue<GLDS, false>(reinterpret_cast<const char*>(key_step + r * GROUP), ring_w + slot_of(i, r) * GROUP,
+                            lane_b);
   };
   if (n > 0) {
 #pragma unroll
@@ -231,7 +206,7 @@ pbs512k4_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_idx
           fwd_p3_tw(tw3, T, lane);
           // sub > 0: everyone has read my previous spectra before this transform's first LDS write
           fft512_fwd_tw(vv, xch, lane, tw2, tw3, 0, [&]() __attribute__((always_inline)) {
-            if (sub > 0) k4_wait(tflags, ctl, role, tcnt, guard);
+            if (sub > 0) group_wait<4>(tf, role, tcnt, guard);
           });
           // unzip: E_0 = Z[sl] + Z[sl + 4], E_1 = conj(tz) (Z[sl] - Z[sl + 4])
 #pragma unroll
@@ -243,24 +218,24 @@ pbs512k4_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_idx
         }
         // the last digit polynomial's spectra are published by the first key window's barrier
         if (sub + 1 < NF) {
-          k4_sync(tflags, ctl, role, tcnt, guard);
+          group_sync_composed<4>(tf, role, tcnt, guard);
 #pragma unroll
           for (int row = 0; row < K1; ++row) X[row][sub] = myslot[(row >> 1) * XS + (row & 1) * SL * 64];
 #pragma unroll
           for (int row = 0; row < K1; ++row) pin(X[row][sub]);
-          k4_signal(tflags, ctl, role, tcnt);
+          group_signal<4>(tf, role, tcnt);
         }
       }
     } else {
       // role 3: the owners' spectra of all but the last digit polynomial
 #pragma unroll
       for (int f = 0; f + 1 < NF; ++f) {
-        k4_sync(tflags, ctl, role, tcnt, guard);
+        group_sync_composed<4>(tf, role, tcnt, guard);
 #pragma unroll
         for (int row = 0; row < K1; ++row) X[row][f] = myslot[(row >> 1) * XS + (row & 1) * SL * 64];
 #pragma unroll
         for (int row = 0; row < K1; ++row) pin(X[row][f]);
-        k4_signal(tflags, ctl, role, tcnt);
+        group_signal<4>(tf, role, tcnt);
       }
     }
 
@@ -358,10 +333,10 @@ pbs512k4_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_idx
         // role 3 only mails: it publishes, and the next window's barrier keeps it from mailing
         // into a scratch its owner still transforms in
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        k4_signal(tflags, ctl, role, tcnt);
+        group_signal<4>(tf, role, tcnt);
         return;
       }
-      k4_sync(tflags, ctl, role, tcnt, guard);
+      group_sync_composed<4>(tf, role, tcnt, guard);
       // zip: Z[sl] = E_0 + tz E_1, Z[sl + 4] = E_0 - tz E_1 (role 2's second half has no mail: 0)
       cplx V[8];
 #pragma unroll
@@ -416,10 +391,7 @@ pbs512k4_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_idx
     }
   }
 
-  if constexpr (RESID) {
-    for (int off = 32; off > 0; off >>= 1) max_resid = fmax(max_resid, __shfl_xor(max_resid, off));
-    if (lane == 0 && active && resid_out) atomicMax(resid_out, (unsigned long long)__double_as_longlong(max_resid));
-  }
+  if constexpr (RESID) report_resid(max_resid, lane, active, resid_out);
 }
 
 // Many levels (l = K4_MANY_MIN .. 64, runtime), whole digits: one level at a time.  Per level the
@@ -440,7 +412,7 @@ pbs512k4_many_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ ou
   constexpr int NW = 4 * K4_CTS;
   constexpr int GROUP = K1 * M;             // (level, limb, column): the five row spectra
   constexpr int WPL = LIMBS * K1;           // key windows per level
-  constexpr uint64_t MAGIC_ALL = k4_magic_all(LIMBS, LB);
+  constexpr uint64_t MAGIC_ALL = limb_magic_all(LIMBS, LB);
   constexpr int RS = K4_RING_SLOTS, DIST = RS - 1;
   constexpr int GLDS = 4;
   constexpr int NISS = GROUP / 64 / GLDS;
@@ -461,6 +433,7 @@ pbs512k4_many_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ ou
   const int ctl = w >> 2;
   const int role = ctl == 0 ? (w & 3) : ((w + 1) & 3);
   const bool owner = role < 3;
+  uint32_t* tf = tflags + ctl * 4;          // this ciphertext's four counters
   const int v = owner ? role : 0;
   const int pl = lane & 1, pa = 2 * v + pl, jb = lane >> 1;
   const uint32_t s = blockIdx.x * K4_CTS + ctl;
@@ -478,12 +451,8 @@ pbs512k4_many_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ ou
   // NGRP is a multiple of RS, so the ring slot is g % RS
   auto issue_group = [&](const cplx* key_step, uint32_t g) __attribute__((always_inline)) {
     if (!issuer) return;
-    const char* src = reinterpret_cast<const char*>(key_step + (uint64_t)g * GROUP);
-    cplx* dst = ring_w + (g % RS) * GROUP;
-#pragma unroll
-    for (int j = 0; j < GLDS; ++j)
-      __builtin_amdgcn_global_load_lds(reinterpret_cast<const cplx*>(src + j * 1024 + lane_b),
-                                       (lds_ptr_t)(dst + j * 64), 16, 0, 0);
+    ring_issue<GLDS, false>(reinterpret_cast<const char*>(key_step + (uint64_t)g * GROUP),
+                            ring_w + (g % RS) * GROUP, lane_b);
   };
   if (n > 0) {
 #pragma unroll
@@ -615,7 +584,7 @@ pbs512k4_many_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ ou
 #pragma unroll
       for (int cc = 0; cc < K1; ++cc) myslot[(cc >> 1) * XS + (cc & 1) * SL * 64] = Y[li][cc];
       if (owner) {
-        k4_sync(tflags, ctl, role, tcnt, guard);
+        group_sync_composed<4>(tf, role, tcnt, guard);
         cplx V[8];
 #pragma unroll
         for (int sl = 0; sl < SL; ++sl) {
@@ -648,7 +617,7 @@ pbs512k4_many_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ ou
         for (int m = 0; m < 16; ++m) pin(A[m]);
       } else {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        k4_signal(tflags, ctl, role, tcnt);
+        group_signal<4>(tf, role, tcnt);
       }
       // every owner is done with its scratch (the next limb's mail, the next step's rotation)
       pair_barrier();
@@ -672,27 +641,12 @@ pbs512k4_many_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ ou
     }
   }
 
-  if constexpr (RESID) {
-    for (int off = 32; off > 0; off >>= 1) max_resid = fmax(max_resid, __shfl_xor(max_resid, off));
-    if (lane == 0 && active && resid_out) atomicMax(resid_out, (unsigned long long)__double_as_longlong(max_resid));
-  }
+  if constexpr (RESID) report_resid(max_resid, lane, active, resid_out);
 }
 
 template <int SUBS, int NQ, int LIMBS, bool RESID>
 static int launch_k4_t(const PbsArgs& a) {
-  const size_t lds = pbs512k4_lds_bytes();
-  auto kern = pbs512k4_kernel<SUBS, NQ, LIMBS, RESID>;
-  CHIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const uint32_t blocks = (a.num_samples + K4_CTS - 1) / K4_CTS;
-  hipLaunchKernelGGL(kern, dim3(blocks), dim3(K4_CTS * 256), lds, a.stream, a.out, a.out_idx, a.luts, a.lut_idx,
-                     a.in, a.in_idx, reinterpret_cast<const cplx*>(a.fbsk), a.n, a.base_log, a.num_samples, a.resid,
-                     a.guard);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("pbs launch failed: %s", hipGetErrorString(e));
-    return -1;
-  }
-  return 0;
+  return launch_fused(pbs512k4_kernel<SUBS, NQ, LIMBS, RESID>, K4_CTS, K4_CTS * 256, pbs512k4_lds_bytes(), a);
 }
 
 template <int SUBS, int NQ, int LIMBS = 4>
@@ -702,19 +656,7 @@ static int launch_k4_r(const PbsArgs& a) {
 
 template <bool RESID>
 static int launch_k4_many_t(const PbsArgs& a) {
-  const size_t lds = pbs512k4_lds_bytes();
-  auto kern = pbs512k4_many_kernel<RESID>;
-  CHIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const uint32_t blocks = (a.num_samples + K4_CTS - 1) / K4_CTS;
-  hipLaunchKernelGGL(kern, dim3(blocks), dim3(K4_CTS * 256), lds, a.stream, a.out, a.out_idx, a.luts, a.lut_idx,
-                     a.in, a.in_idx, reinterpret_cast<const cplx*>(a.fbsk), a.n, a.level, a.base_log,
-                     a.num_samples, a.resid, a.guard);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("pbs launch failed: %s", hipGetErrorString(e));
-    return -1;
-  }
-  return 0;
+  return launch_fused(pbs512k4_many_kernel<RESID>, K4_CTS, K4_CTS * 256, pbs512k4_lds_bytes(), a);
 }
 
 int pbs512k4_launch(const PbsArgs& a) {

@@ -1944,6 +1944,7 @@ __global__ void __launch_bounds__(512) gen_coop_kernel(CoopArgs a) {
   auto consume = [&](uint32_t ev) __attribute__((always_inline)) {
     if (COOP_DIAG_NOSYNC) return;
     if (w == 0) {
+      // the bounded spin of kernel_util.hpp spin_until_ge, on an agent-scope flag and flagging from lane 0 only
       for (uint32_t it = 0;; ++it) {
         if (__hip_atomic_load(pflag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= ev) break;
         if (it >= a.spin_limit) {

@@ -28,6 +28,7 @@
 #include "fft512.hpp"
 #include "kernel_util.hpp"
 #include "pbs.hpp"
+#include "pbs_launch.hpp"
 
 #include <type_traits>
 
@@ -50,28 +51,9 @@ namespace chip {
 
 namespace {
 
-constexpr uint64_t SM_MAGIC_ALL =
-    RND_MAGIC_BITS + (RND_MAGIC_BITS << 16) + (RND_MAGIC_BITS << 32) + (RND_MAGIC_BITS << 48);
-
-// the two waves of one ciphertext (counters f[ct * 2 + v])
-__device__ __forceinline__ void sm_sync(uint32_t* f, int ct, int v, uint32_t& cnt, const SyncGuard& guard) {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  ++cnt;
-  __hip_atomic_store(&f[ct * 2 + v], cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  spin_until_ge(&f[ct * 2 + (v ^ 1)], cnt, guard);
-}
-__device__ __forceinline__ void sm_signal(uint32_t* f, int ct, int v, uint32_t& cnt) {
-  asm volatile("" ::: "memory");
-  ++cnt;
-  __hip_atomic_store(&f[ct * 2 + v], cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-__device__ __forceinline__ void sm_wait(uint32_t* f, int ct, int v, uint32_t cnt, const SyncGuard& guard) {
-  spin_until_ge(&f[ct * 2 + (v ^ 1)], cnt, guard);
-  asm volatile("" ::: "memory");
-}
-
-__device__ __forceinline__ cplx mul_i(cplx a) { return {-a.im, a.re}; }
-__device__ __forceinline__ cplx mul_mi(cplx a) { return {a.im, -a.re}; }
+static_assert(limb_magic_all(4, 16) ==
+                  RND_MAGIC_BITS + (RND_MAGIC_BITS << 16) + (RND_MAGIC_BITS << 32) + (RND_MAGIC_BITS << 48),
+              "four 16-bit limbs");
 
 // P-point DFTs over the slots of one lane: unzip F_p = sum_q w_P^{-pq} Y_q, zip Y_q = sum_p w_P^{pq} F_p
 // (w_P = exp(-2 pi i / P), unnormalised)
@@ -85,7 +67,7 @@ __device__ __forceinline__ void dftp(cplx (&x)[P], bool inverse) {
     static_assert(P == 4, "P = 2 or 4");
     const cplx s02 = cadd(x[0], x[2]), d02 = csub(x[0], x[2]);
     const cplx s13 = cadd(x[1], x[3]), d13 = csub(x[1], x[3]);
-    const cplx r = inverse ? mul_i(d13) : mul_mi(d13);  // i^{pq} (unzip) or (-i)^{pq} (zip) at p q = 1
+    const cplx r = inverse ? mul_mi<true>(d13) : mul_mi<false>(d13);  // i^{pq} (unzip) or (-i)^{pq} (zip) at p q = 1
     x[0] = cadd(s02, s13);
     x[2] = csub(s02, s13);
     x[1] = cadd(d02, r);
@@ -138,6 +120,7 @@ pbs_small_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_id
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   const int ctl = w >> 1, v = w & 1;
+  uint32_t* sf = sflags + ctl * 2;          // sync group (group_*<2>): the two waves of this ciphertext
   const int pl = lane & (P - 1);            // my lane's polynomial (local)
   const int pa = v * P + pl;                // ... absolute (>= K1: an empty slot of the last wave)
   const int jb = lane / P;                  // coefficient index base: j(m) = jb + (64 / P) m
@@ -154,12 +137,13 @@ pbs_small_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_id
   auto issue_group = [&](const cplx* key_step, int r) __attribute__((always_inline)) {
     const char* src = reinterpret_cast<const char*>(key_step + r * GROUP);
     cplx* dst = ring_w + (r % RS) * GROUP;
+    if constexpr (PB == 16) {
+      ring_issue<GLDS, false>(src, dst, lane_b);
+    } else {  // groups that do not split into 1 KB pieces per wave: 256-byte pieces, 4 bytes per lane
 #pragma unroll
-    for (int j = 0; j < GLDS; ++j) {
-      const void* gp = src + j * 64 * PB + lane_b;
-      lds_ptr_t lp = (lds_ptr_t)(reinterpret_cast<char*>(dst) + j * 64 * PB);
-      if constexpr (PB == 16) __builtin_amdgcn_global_load_lds(gp, lp, 16, 0, 0);
-      else __builtin_amdgcn_global_load_lds(gp, lp, 4, 0, 0);
+      for (int j = 0; j < GLDS; ++j)
+        __builtin_amdgcn_global_load_lds(src + j * 256 + lane_b, (lds_ptr_t)(reinterpret_cast<char*>(dst) + j * 256), 4,
+                                         0, 0);
     }
   };
   if (n > 0) {
@@ -265,7 +249,7 @@ pbs_small_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_id
         fwd_p3_tw(tw3, T, lane);
         if (!SMD_NOFWD)
           fft512_fwd_tw(vv, xch, lane, tw2, tw3, 0, [&]() __attribute__((always_inline)) {
-            if (sub > 0) sm_wait(sflags, ctl, v, scnt, guard);
+            if (sub > 0) group_wait<2>(sf, v, scnt, guard);
           });
         // unzip: E_p = conj(tz_p) sum_q w_P^{-pq} Z[slot sl + q SL]
 #pragma unroll
@@ -281,7 +265,7 @@ pbs_small_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_id
       }
       // the last digit polynomial's spectra are published by the first key window's barrier
       if (sub + 1 < NF) {
-        sm_sync(sflags, ctl, v, scnt, guard);
+        group_sync<2>(sf, v, scnt, guard);
 #pragma unroll
         for (int row = 0; row < K1; ++row)
 #pragma unroll
@@ -291,7 +275,7 @@ pbs_small_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_id
         for (int row = 0; row < K1; ++row)
 #pragma unroll
           for (int js = 0; js < MS; ++js) pin(X[row][sub][js]);
-        sm_signal(sflags, ctl, v, scnt);
+        group_signal<2>(sf, v, scnt);
       }
     }
 
@@ -427,7 +411,7 @@ pbs_small_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_id
           }
         }
       }
-      sm_sync(sflags, ctl, v, scnt, guard);
+      group_sync<2>(sf, v, scnt, guard);
       cplx V[8];
 #pragma unroll
       for (int sl = 0; sl < SL; ++sl) {
@@ -455,8 +439,8 @@ pbs_small_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_id
           max_resid = fmax(max_resid, fabs(V[m].im - (ti - RND_MAGIC)));
         }
         if constexpr (li == 0) {
-          A[m] += (uint64_t)__double_as_longlong(tr) - SM_MAGIC_ALL;
-          A[m + 8] += (uint64_t)__double_as_longlong(ti) - SM_MAGIC_ALL;
+          A[m] += (uint64_t)__double_as_longlong(tr) - limb_magic_all(SM_LIMBS, SM_SUB_BITS);
+          A[m + 8] += (uint64_t)__double_as_longlong(ti) - limb_magic_all(SM_LIMBS, SM_SUB_BITS);
         } else {
           A[m] += (uint64_t)__double_as_longlong(tr) << (16 * li);
           A[m + 8] += (uint64_t)__double_as_longlong(ti) << (16 * li);
@@ -487,27 +471,12 @@ pbs_small_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_id
     }
   }
 
-  if constexpr (RESID) {
-    for (int off = 32; off > 0; off >>= 1) max_resid = fmax(max_resid, __shfl_xor(max_resid, off));
-    if (lane == 0 && active && resid_out) atomicMax(resid_out, (unsigned long long)__double_as_longlong(max_resid));
-  }
+  if constexpr (RESID) report_resid(max_resid, lane, active, resid_out);
 }
 
 template <int N, int K1, int SUBS, int NQ, bool RESID>
 static int launch_small_t(const PbsArgs& a) {
-  const size_t lds = pbs_small_lds_bytes(N, K1);
-  auto kern = pbs_small_kernel<N, K1, SUBS, NQ, RESID>;
-  CHIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const uint32_t blocks = (a.num_samples + SM_CTS - 1) / SM_CTS;
-  hipLaunchKernelGGL(kern, dim3(blocks), dim3(SM_CTS * 128), lds, a.stream, a.out, a.out_idx, a.luts, a.lut_idx, a.in,
-                     a.in_idx, reinterpret_cast<const cplx*>(a.fbsk), a.n, a.base_log, a.num_samples, a.resid,
-                     a.guard);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("pbs launch failed: %s", hipGetErrorString(e));
-    return -1;
-  }
-  return 0;
+  return launch_fused(pbs_small_kernel<N, K1, SUBS, NQ, RESID>, SM_CTS, SM_CTS * 128, pbs_small_lds_bytes(N, K1), a);
 }
 
 template <int N, int K1, int SUBS, int NQ>
