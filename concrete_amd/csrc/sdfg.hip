@@ -24,6 +24,9 @@
 //     every device after first use.
 // Device list: CONCRETE_HIP_SDFG_DEVICES="0,0,1" (entries may repeat), else SDFG_NUM_GPUS (first
 // N visible devices, capped at the visible count as GPUDFG.cpp:1745-1758), else every device.
+// CONCRETE_HIP_SDFG_TRACE=1 prints each evaluated subgraph; CONCRETE_HIP_SDFG_CHUNK_SAMPLES=<k>
+// caps the samples per chunk of a shard (tests: the chunk loop without filling the device), read at
+// every get.
 #include <stdarg.h>
 #include <string.h>
 
@@ -483,13 +486,17 @@ void execute(Dfg* g, Stream* target) {
     shard[r].start = r * base + std::min<uint64_t>(r, extra);
   }
   const uint64_t per_sample = bytes_per_sample(P);
+  // test hook, read per get (not cached): at most this many samples per chunk
+  uint64_t chunk_cap = 0;
+  if (const char* e = getenv("CONCRETE_HIP_SDFG_CHUNK_SAMPLES")) chunk_cap = strtoull(e, nullptr, 10);
   auto work = [&](uint64_t r) {
     Slot& sl = g->slots[r];
     CHIP_CHECK(hipSetDevice((int)sl.gpu));
     size_t free_b = 0, total_b = 0;
     CHIP_CHECK(hipMemGetInfo(&free_b, &total_b));
     // half of the free memory for this shard's chunks (several shards may share the device)
-    const uint64_t chunk = std::max<uint64_t>(1, (uint64_t)(free_b / 2 / parts) / per_sample);
+    uint64_t chunk = std::max<uint64_t>(1, (uint64_t)(free_b / 2 / parts) / per_sample);
+    if (chunk_cap) chunk = std::min(chunk, chunk_cap);
     for (uint64_t s0 = 0; s0 < shard[r].count; s0 += chunk)
       run_chunk(P, sl, shard[r].start + s0, std::min(chunk, shard[r].count - s0));
     // the shard stream's own status read (no device-wide synchronisation)

@@ -205,6 +205,9 @@ class Dfg:
     def put_uint64(self, s, v: int):
         self.lib.stream_emulator_put_uint64(s, int(v))
 
+    def get_uint64(self, s) -> int:
+        return int(self.lib.stream_emulator_get_uint64(s))
+
     def get_batch(self, s, rows, cols, out=None) -> np.ndarray:
         """The stream's (rows, cols) batch, into `out` when given (C-contiguous uint64 of that shape)."""
         if out is None:

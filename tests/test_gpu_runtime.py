@@ -436,3 +436,69 @@ def test_wide_digits_on_the_general_path(env, level, base_log):
     L.cuda_drop(d_bsk, 0)
     L.cuda_destroy_stream(s, 0)
     assert np.array_equal(out, ref) and np.array_equal(out2, ref)
+
+
+def test_memref_offsets_and_padded_lut_rows(env):
+    """The memref descriptors a circuit may pass: ct0, out and tlu inside larger allocations
+    (non-zero offsets) and, for the mapped bootstrap, LUT rows N + 8 words apart.  Each call is
+    bit-exact against the same call on dense copies and against the oracle, and writes nothing
+    outside its output rows."""
+    B, R, O, p = env["B"], env["R"], env["O"], env["p"]
+    width = 2
+    nb = 7
+    W = p.big_n + 1
+    SENT = np.uint64(0x5EA15EA15EA15EA1)
+    rng = np.random.RandomState(11)
+    msgs, cts = inputs(env, nb, width, 600)
+    tables = [rng.randint(0, 4, size=4).astype(np.uint64) for _ in range(nb)]
+    tlus = np.stack([B.expand_lut(t, p.N, width) for t in tables])
+    accs = np.stack([B.trivial_glwe(p, t) for t in tlus])
+
+    def inside(a, offset, row_stride=None):
+        """A flat allocation of noise holding the rows of `a` from `offset` on, `row_stride` apart."""
+        a = np.atleast_2d(a)
+        rs = row_stride or a.shape[1]
+        flat = rng.randint(1, 1 << 62, size=offset + a.shape[0] * rs + 5).astype(np.uint64)
+        for r, row in enumerate(a):
+            flat[offset + r * rs: offset + r * rs + a.shape[1]] = row
+        return flat
+
+    def ptr2(a):
+        return [a.ctypes.data, a.ctypes.data]
+
+    def payload(out, offset, rows, cols):
+        body = out[offset: offset + rows * cols].reshape(rows, cols)
+        assert np.all(out[:offset] == SENT) and np.all(out[offset + rows * cols:] == SENT)
+        return body
+
+    ks = keyset(env, [0, 0])
+    try:
+        ct_f, tlu_f, tlus_f = inside(cts, 3), inside(tlus[0], 9), inside(tlus, 6, p.N + 8)
+        # one LUT for the batch
+        out = np.full(7 + nb * W + 4, SENT, dtype=np.uint64)
+        ks.lib.memref_batched_bootstrap_lwe_hip_u64(*ptr2(out), 7, nb, W, W, 1, *ptr2(ct_f), 3, nb, p.n + 1, p.n + 1, 1,
+                                                    *ptr2(tlu_f), 9, p.N, 1, p.n, p.N, p.level, p.base_log, p.k, 0,
+                                                    ks.h)
+        big = payload(out, 7, nb, W).copy()
+        ref, _ = O.pbs_batch(env["op"], cts, accs[:1], fbsk=env["fcpu"])
+        assert np.array_equal(big, ref) and np.array_equal(big, R.batched_bootstrap(ks, p, cts, tlus[0]))
+        # one LUT row per sample, rows N + 8 apart
+        out[:] = SENT
+        ks.lib.memref_batched_mapped_bootstrap_lwe_hip_u64(*ptr2(out), 7, nb, W, W, 1, *ptr2(ct_f), 3, nb, p.n + 1,
+                                                           p.n + 1, 1, *ptr2(tlus_f), 6, nb, p.N, p.N + 8, 1, p.n, p.N,
+                                                           p.level, p.base_log, p.k, 0, ks.h)
+        mapped = payload(out, 7, nb, W).copy()
+        refm, _ = O.pbs_batch(env["op"], cts, accs, fbsk=env["fcpu"], lut_idx=np.arange(nb, dtype=np.uint64))
+        assert np.array_equal(mapped, refm) and np.array_equal(mapped, R.batched_mapped_bootstrap(ks, p, cts, tlus))
+        dec = B.lwe_decrypt(env["glwe_sk"], mapped, p.big_n)
+        assert [B.decode(d, width) for d in dec] == [int(tables[i][m]) for i, m in enumerate(msgs)]
+        # keyswitch
+        big_f = inside(big, 5)
+        small = np.full(2 + nb * (p.n + 1) + 3, SENT, dtype=np.uint64)
+        ks.lib.memref_batched_keyswitch_lwe_hip_u64(*ptr2(small), 2, nb, p.n + 1, p.n + 1, 1, *ptr2(big_f), 5, nb, W, W,
+                                                    1, p.ks_level, p.ks_base_log, p.big_n, p.n, 0, ks.h)
+        got = payload(small, 2, nb, p.n + 1)
+        assert np.array_equal(got, O.keyswitch_batch(env["op"], big, env["ksk"]))
+        assert np.array_equal(got, R.batched_keyswitch(ks, p, big))
+    finally:
+        ks.close()
