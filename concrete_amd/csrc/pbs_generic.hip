@@ -30,6 +30,7 @@
 #include <cmath>
 #include <map>
 #include <mutex>
+#include <utility>
 #include <vector>
 
 #include "common.hpp"
@@ -135,7 +136,21 @@ bool generic_pbs_ok(uint32_t k, uint32_t N, uint32_t level, uint32_t base_log) {
   return generic_error_bound(k, N, level, base_log, f.bits, 0.0) < 0.25;
 }
 
-static hipStream_t side_stream(int idx);  // a library stream per device (defined below)
+// A second stream per device for the two-launch and split paths' chunk groups (created once, never
+// destroyed: it lives as long as the process, like the device tables).
+static hipStream_t side_stream(int idx) {
+  static std::mutex mu;
+  static std::map<std::pair<int, int>, hipStream_t> streams;
+  int dev = 0;
+  CHIP_CHECK(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> g(mu);
+  auto it = streams.find({dev, idx});
+  if (it != streams.end()) return it->second;
+  hipStream_t s = nullptr;
+  CHIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  streams[{dev, idx}] = s;
+  return s;
+}
 
 namespace gen {
 
@@ -147,7 +162,132 @@ __device__ __forceinline__ cplx ld_once(const cplx* p) {
   return *p;
 #endif
 }
+// a value written once for the next launch: streaming store when GEN_NT_STORES >= LEVEL (ST_XY: the
+// two-launch path's X and Y spectra; ST_ALL: the accumulators and the split path's spectra as well)
+constexpr int ST_XY = 1, ST_ALL = 2;
+template <int LEVEL>
+__device__ __forceinline__ void st_once(cplx* p, cplx v) {
+  if constexpr (GEN_NT_STORES >= LEVEL) {
+    __builtin_nontemporal_store(v.re, &p->re);
+    __builtin_nontemporal_store(v.im, &p->im);
+  } else {
+    *p = v;
+  }
+}
+template <int LEVEL>
+__device__ __forceinline__ void st_once(uint64_t* p, uint64_t v) {
+  if constexpr (GEN_NT_STORES >= LEVEL) __builtin_nontemporal_store(v, p);
+  else *p = v;
+}
 
+// ------------------------------------------------------------------------------------------
+// arithmetic shared by every kernel family below
+// ------------------------------------------------------------------------------------------
+
+// tfhe SignedDecomposer::decompose_one_level: on a 32-bit state (level * base_log <= 31,
+// narrow_state) or a 64-bit one (digits up to 64 bits)
+template <class St>
+__device__ __forceinline__ auto decomp_next(St& state, int logB) {
+  if constexpr (sizeof(St) == 4) {
+    return decomp_next_t<uint32_t>(state, logB);
+  } else {
+    const uint64_t mask = logB >= 64 ? ~0ull : (1ull << logB) - 1ull;
+    const uint64_t res = state & mask;
+    state = logB >= 64 ? 0ull : state >> logB;
+    const uint64_t carry = (((res - 1ull) | state) & res) >> (logB - 1);
+    state += carry;
+    return (int64_t)(res - (logB >= 64 ? 0ull : carry << logB));
+  }
+}
+
+// Balanced b-bit sub-digits of a decomposition digit, d = sum_t 2^{tb} s_t with |s_t| <= 2^(b-1): take()
+// returns the next one and leaves the quotient in D (exact: D - s is a multiple of 2^b).  With one
+// sub-digit, half = 0 and an all-ones mask make s = D and leave D = 0, so there is no per-element
+// branch.  BRANCH (gen_step_kernel): a one-sub-digit call skips the arithmetic instead.
+template <class St, bool BRANCH = false>
+struct SubDigit {
+  using Dg = typename std::make_signed<St>::type;
+  St half, bmask;
+  int sb;
+  bool split;
+  __device__ __forceinline__ SubDigit(uint32_t bits, bool split_)
+      : half(split_ ? (St)1 << (bits - 1) : (St)0),
+        bmask(split_ ? ((St)1 << bits) - (St)1 : ~(St)0),
+        sb((int)bits),
+        split(split_) {}
+  template <class V>  // V = Dg, or St for an unsigned value (the key converters)
+  __device__ __forceinline__ Dg take(V& D) const {
+    if (BRANCH && !split) return (Dg)D;
+    const Dg s = (Dg)(((St)D + half) & bmask) - (Dg)half;
+    D = (D - (V)s) >> sb;
+    return s;
+  }
+};
+
+// acc += 2^sh round(v), both halves, and the rounding residual |v - round(v)| tracked:
+// bits(x + MAGIC) - MAGIC_BITS = round(x) mod 2^64 for |x| < 2^51 (either sign).  No guard on the
+// shift: slot m < L is added at sh = m b, and generic_key_format sets L = ceil(64 / b), so
+// (L - 1) b < 64 (the top limb is 64 - (L - 1) b >= 1 bits wide) for every format the gate admits.
+__device__ __forceinline__ void round_acc(cplx v, uint32_t sh, uint64_t& re_acc, uint64_t& im_acc, double& max_resid) {
+  const double tr = v.re + RND_MAGIC, ti = v.im + RND_MAGIC;
+  max_resid = fmax(max_resid, fmax(fabs(v.re - (tr - RND_MAGIC)), fabs(v.im - (ti - RND_MAGIC))));
+  re_acc += ((uint64_t)__double_as_longlong(tr) - RND_MAGIC_BITS) << sh;
+  im_acc += ((uint64_t)__double_as_longlong(ti) - RND_MAGIC_BITS) << sh;
+}
+
+// coefficient x (any x: taken mod 2N) of the negacyclic extension of the N-coefficient polynomial p
+// (X^N = -1: bit N of x is the sign).  neg_at_rows: p in the four-step row order (coefficient n at
+// (n mod R) N/R + n / R)
+template <int N>
+__device__ __forceinline__ uint64_t neg_at(const uint64_t* p, uint32_t x) {
+  const uint64_t v = p[x & (N - 1)];
+  return (x & N) == 0 ? v : 0ull - v;
+}
+template <int N, int LOGR>
+__device__ __forceinline__ uint64_t neg_at_rows(const uint64_t* p, uint32_t x) {
+  const uint32_t idx = x & (N - 1);
+  const uint64_t v = p[(idx & ((1 << LOGR) - 1)) * (N >> LOGR) + (idx >> LOGR)];
+  return (x & N) == 0 ? v : 0ull - v;
+}
+
+// R-point DFT in registers, natural order in and out (forward exp(-2 pi i jk/R), inverse +): the
+// butterfly of the LDS passes (R = 2, 4, 8) and the four-step column DFT across the rows (R <= 16)
+constexpr double C16_1 = 0.92387953251128675613, S16_1 = 0.38268343236508977173;  // cos, sin pi/8
+constexpr double R2H = 0.70710678118654752440;
+template <int R, bool INV>
+__device__ __forceinline__ void butterfly(cplx (&u)[R]) {
+  if constexpr (R == 2) {
+    const cplx x0 = u[0], x1 = u[1];
+    u[0] = cadd(x0, x1);
+    u[1] = csub(x0, x1);
+  } else if constexpr (R == 4) {
+    const cplx t0 = cadd(u[0], u[2]), t1 = csub(u[0], u[2]);
+    const cplx t2 = cadd(u[1], u[3]), t3 = mul_mi<INV>(csub(u[1], u[3]));
+    u[0] = cadd(t0, t2);
+    u[2] = csub(t0, t2);
+    u[1] = cadd(t1, t3);
+    u[3] = csub(t1, t3);
+  } else if constexpr (R == 8) {
+    dft8<INV>(u);
+  } else {
+    static_assert(R == 16, "radix");
+    // even / odd halves, then X[k] = E[k] + w16^k O[k], X[k + 8] = E[k] - w16^k O[k]
+    cplx e[8], o[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) e[i] = u[2 * i], o[i] = u[2 * i + 1];
+    dft8<INV>(e);
+    dft8<INV>(o);
+    const cplx w16[8] = {{1.0, 0.0},     {C16_1, -S16_1}, {R2H, -R2H},     {S16_1, -C16_1},
+                         {0.0, -1.0},    {-S16_1, -C16_1}, {-R2H, -R2H},   {-C16_1, -S16_1}};
+#pragma unroll
+    for (int k = 1; k < 8; ++k) o[k] = k == 4 ? mul_mi<INV>(o[4]) : INV ? cmulc(o[k], w16[k]) : cmul(o[k], w16[k]);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      u[k] = cadd(e[k], o[k]);
+      u[k + 8] = csub(e[k], o[k]);
+    }
+  }
+}
 
 // ------------------------------------------------------------------------------------------
 // block FFT (LDS, in place, radix-8 Stockham passes after one radix-2/4 pass; radix-4 for M <= 256)
@@ -164,12 +304,13 @@ struct Geo {
   static_assert(VPT % 4 == 0, "values per thread");
 };
 
-// Synchronisation of one polynomial's threads around its LDS passes: a polynomial of up to 64
-// threads lives in one wave, whose LDS operations execute in issue order, so only the compiler
-// has to be fenced; larger polynomials span waves and take a workgroup barrier.
-template <int M>
-__device__ __forceinline__ void poly_sync() {
-  if constexpr (Geo<M>::THREADS <= 64) wave_lds_fence();
+// Synchronisation of the TH threads of one polynomial around its LDS passes: a polynomial of up to
+// 64 threads lives in one wave, whose LDS operations execute in issue order, so only the compiler
+// has to be fenced; larger polynomials span waves and take a workgroup barrier (every polynomial of
+// the workgroup transforms in lockstep).
+template <int TH>
+__device__ __forceinline__ void lds_sync() {
+  if constexpr (TH <= 64) wave_lds_fence();
   else __syncthreads();
 }
 
@@ -207,11 +348,15 @@ __device__ __forceinline__ void load_twiddles(cplx* tw, const cplx* Wfull, const
 // bank groups per 8-lane group (gfx950 ds_write_b128/ds_read_b128 lane groups).
 __device__ __forceinline__ int sw(int i) { return i ^ (((i >> 4) & 7) << 1); }
 
-// One Stockham pass of radix R at stride Ns (natural order in, natural order out).  Every
-// thread reads all its inputs before the barrier and writes after it, so the pass is in place.
-template <int M, int R, bool INV>
-__device__ __forceinline__ void stockham_pass(cplx* buf, const cplx* W, int tid, int Ns) {
-  constexpr int TH = Geo<M>::THREADS;
+// One Stockham pass of radix R at stride Ns (natural order in, natural order out) by the TH threads
+// of a polynomial.  Every thread reads all its inputs before the barrier and writes after it, so
+// the pass is in place.  Twiddles W[kk r M / (Ns R)], kk = j mod Ns, from one of two layouts:
+//   TW_TABLE  the whole table W (twiddle<M, INV>: full, or two-level past FULL_TW_MAX);
+//   TW_PASS   this pass's own table, W[kk (R - 1) + r - 1] (build_tile_tw);
+//   TW_ONE    a first pass of the per-pass layout (Ns = 1: all twiddles 1, nothing multiplied).
+enum { TW_TABLE, TW_PASS, TW_ONE };
+template <int M, int TH, int R, bool INV, int TW>
+__device__ __forceinline__ void lds_pass(cplx* buf, const cplx* W, int tid, int Ns) {
   constexpr int NB = M / R / TH;  // butterflies per thread
   static_assert(NB >= 1 && (M / R) % TH == 0, "pass split");
   cplx v[NB][R];
@@ -221,61 +366,56 @@ __device__ __forceinline__ void stockham_pass(cplx* buf, const cplx* W, int tid,
 #pragma unroll
     for (int r = 0; r < R; ++r) v[s][r] = buf[sw(j + r * (M / R))];
   }
-  poly_sync<M>();
+  lds_sync<TH>();
 #pragma unroll
   for (int s = 0; s < NB; ++s) {
     const int j = tid + s * TH;
-    const int kk = j & (Ns - 1);
-    const int step = M / (Ns * R);
+    const int kk = TW == TW_ONE ? 0 : (j & (Ns - 1));
+    if constexpr (TW == TW_TABLE) {
+      const int step = M / (Ns * R);
 #pragma unroll
-    for (int r = 1; r < R; ++r) v[s][r] = cmul(v[s][r], twiddle<M, INV>(W, kk * r * step));
-    if constexpr (R == 2) {
-      const cplx x0 = v[s][0], x1 = v[s][1];
-      v[s][0] = cadd(x0, x1);
-      v[s][1] = csub(x0, x1);
-    } else if constexpr (R == 4) {
-      const cplx t0 = cadd(v[s][0], v[s][2]), t1 = csub(v[s][0], v[s][2]);
-      const cplx t2 = cadd(v[s][1], v[s][3]), t3 = mul_mi<INV>(csub(v[s][1], v[s][3]));
-      v[s][0] = cadd(t0, t2);
-      v[s][2] = csub(t0, t2);
-      v[s][1] = cadd(t1, t3);
-      v[s][3] = csub(t1, t3);
-    } else {
-      dft8<INV>(v[s]);
+      for (int r = 1; r < R; ++r) v[s][r] = cmul(v[s][r], twiddle<M, INV>(W, kk * r * step));
+    } else if constexpr (TW == TW_PASS) {
+#pragma unroll
+      for (int r = 1; r < R; ++r) {
+        const cplx w = W[kk * (R - 1) + r - 1];
+        v[s][r] = INV ? cmulc(v[s][r], w) : cmul(v[s][r], w);
+      }
     }
+    butterfly<R, INV>(v[s]);
     const int d = (j - kk) * R + kk;
 #pragma unroll
     for (int r = 0; r < R; ++r) buf[sw(d + r * Ns)] = v[s][r];
   }
-  poly_sync<M>();
+  lds_sync<TH>();
 }
 
 // Unnormalised DFT of buf (M complex, natural order) in place: forward e^{-2 pi i jk/M},
 // inverse e^{+2 pi i jk/M}; W[j] = e^{-2 pi i j/M}.  Callers synchronise before the call.
 template <int M, bool INV>
 __device__ __forceinline__ void fft_block(cplx* buf, const cplx* W, int tid) {
-  constexpr int LOG = Geo<M>::LOG;
+  constexpr int LOG = Geo<M>::LOG, TH = Geo<M>::THREADS;
   if constexpr (Geo<M>::VPT >= 8) {
     // radix-8 passes (three 8-point stages in registers per LDS round trip), the leftover
     // factor 2 or 4 first (its stride-1 pass needs no twiddles)
     int Ns = 1;
     if constexpr (LOG % 3 == 1) {
-      stockham_pass<M, 2, INV>(buf, W, tid, Ns);
+      lds_pass<M, TH, 2, INV, TW_TABLE>(buf, W, tid, Ns);
       Ns = 2;
     } else if constexpr (LOG % 3 == 2) {
-      stockham_pass<M, 4, INV>(buf, W, tid, Ns);
+      lds_pass<M, TH, 4, INV, TW_TABLE>(buf, W, tid, Ns);
       Ns = 4;
     }
 #pragma unroll 1
-    for (; Ns < M; Ns *= 8) stockham_pass<M, 8, INV>(buf, W, tid, Ns);
+    for (; Ns < M; Ns *= 8) lds_pass<M, TH, 8, INV, TW_TABLE>(buf, W, tid, Ns);
   } else {
     int Ns = 1;
     if constexpr (LOG & 1) {
-      stockham_pass<M, 2, INV>(buf, W, tid, Ns);
+      lds_pass<M, TH, 2, INV, TW_TABLE>(buf, W, tid, Ns);
       Ns = 2;
     }
 #pragma unroll 1
-    for (; Ns < M; Ns *= 4) stockham_pass<M, 4, INV>(buf, W, tid, Ns);
+    for (; Ns < M; Ns *= 4) lds_pass<M, TH, 4, INV, TW_TABLE>(buf, W, tid, Ns);
   }
 }
 
@@ -297,12 +437,6 @@ __device__ __forceinline__ void fft_block(cplx* buf, const cplx* W, int tid) {
 #endif
 template <int M>
 constexpr int tile_threads() { return M == 512 ? TILE512_TH : Geo<M>::THREADS; }
-template <int TH>
-__device__ __forceinline__ void tile_sync() {
-  if constexpr (TH <= 64) wave_lds_fence();
-  else __syncthreads();  // every polynomial of the tile transforms in lockstep
-}
-
 // radix of the tile transforms' passes (values per thread) and of the first pass (the leftover
 // factor, or a full pass: its twiddles are all 1)
 template <int M, int TH>
@@ -330,71 +464,17 @@ __device__ __forceinline__ void build_tile_tw(cplx* TWP, const cplx* W, int t, i
   }
 }
 
-template <int M, int TH, int R, bool INV, bool FIRST>
-__device__ __forceinline__ void tile_pass(cplx* buf, const cplx* TW, int tid, int Ns) {
-  constexpr int NB = M / R / TH;
-  static_assert(NB >= 1 && (M / R) % TH == 0, "pass split");
-  cplx v[NB][R];
-#pragma unroll
-  for (int s = 0; s < NB; ++s) {
-    const int j = tid + s * TH;
-#pragma unroll
-    for (int r = 0; r < R; ++r) v[s][r] = buf[sw(j + r * (M / R))];
-  }
-  tile_sync<TH>();
-#pragma unroll
-  for (int s = 0; s < NB; ++s) {
-    const int j = tid + s * TH;
-    const int kk = FIRST ? 0 : (j & (Ns - 1));
-    if constexpr (!FIRST) {
-#pragma unroll
-      for (int r = 1; r < R; ++r) {
-        const cplx w = TW[kk * (R - 1) + r - 1];
-        v[s][r] = INV ? cmulc(v[s][r], w) : cmul(v[s][r], w);
-      }
-    }
-    if constexpr (R == 2) {
-      const cplx x0 = v[s][0], x1 = v[s][1];
-      v[s][0] = cadd(x0, x1);
-      v[s][1] = csub(x0, x1);
-    } else if constexpr (R == 4) {
-      const cplx t0 = cadd(v[s][0], v[s][2]), t1 = csub(v[s][0], v[s][2]);
-      const cplx t2 = cadd(v[s][1], v[s][3]), t3 = mul_mi<INV>(csub(v[s][1], v[s][3]));
-      v[s][0] = cadd(t0, t2);
-      v[s][2] = csub(t0, t2);
-      v[s][1] = cadd(t1, t3);
-      v[s][3] = csub(t1, t3);
-    } else {
-      dft8<INV>(v[s]);
-    }
-    const int d = (j - kk) * R + kk;
-#pragma unroll
-    for (int r = 0; r < R; ++r) buf[sw(d + r * Ns)] = v[s][r];
-  }
-  tile_sync<TH>();
-}
-
 template <int M, int TH, bool INV>
 __device__ __forceinline__ void tile_fft(cplx* buf, const cplx* TWP, int tid) {
   constexpr int R = tile_radix<M, TH>(), R0 = tile_first_radix<M, TH>();
   static_assert(R == 4 || R == 8, "tile radix");
-  tile_pass<M, TH, R0, INV, true>(buf, nullptr, tid, 1);
+  lds_pass<M, TH, R0, INV, TW_ONE>(buf, nullptr, tid, 1);
   int off = 0;
 #pragma unroll 1
   for (int Ns = R0; Ns < M; Ns *= R) {
-    tile_pass<M, TH, R, INV, false>(buf, TWP + off, tid, Ns);
+    lds_pass<M, TH, R, INV, TW_PASS>(buf, TWP + off, tid, Ns);
     off += (R - 1) * Ns;
   }
-}
-
-// tfhe SignedDecomposer::decompose_one_level on a 64-bit state (digits up to 64 bits)
-__device__ __forceinline__ int64_t decomp_next64(uint64_t& state, int logB) {
-  const uint64_t mask = logB >= 64 ? ~0ull : (1ull << logB) - 1ull;
-  const uint64_t res = state & mask;
-  state = logB >= 64 ? 0ull : state >> logB;
-  const uint64_t carry = (((res - 1ull) | state) & res) >> (logB - 1);
-  state += carry;
-  return (int64_t)(res - (logB >= 64 ? 0ull : carry << logB));
 }
 
 // ------------------------------------------------------------------------------------------
@@ -474,9 +554,7 @@ __global__ void __launch_bounds__(Geo<M>::BLOCK) gen_step_kernel(StepArgs a) {
     const uint32_t bt = live ? modswitch(lwe[a.n], LOG2_2N) : 0u;
 #pragma unroll
     for (int e = 0; e < 2 * VPT; ++e) {
-      const uint32_t src = (coef(e) + bt) & (2 * N - 1);
-      const uint64_t v = live ? lut[src & (N - 1)] : 0ull;
-      A[e] = src < (uint32_t)N ? v : 0ull - v;
+      A[e] = live ? neg_at<N>(lut, coef(e) + bt) : 0ull;
     }
   } else {
 #pragma unroll
@@ -484,8 +562,7 @@ __global__ void __launch_bounds__(Geo<M>::BLOCK) gen_step_kernel(StepArgs a) {
   }
 
   if constexpr ((MODE & MODE_BACK) != 0) {
-    // acc_c += sum_m 2^{m b} round(iFFT(Y_m) conj(zeta^j)); the key spectra carry the 1/M.
-    // bits(v + MAGIC) - MAGIC_BITS = round(v) mod 2^64 for |v| < 2^51 (either sign).
+    // acc_c += sum_m 2^{m b} round(iFFT(Y_m) conj(zeta^j)); the key spectra carry the 1/M
     const cplx* Yc = a.Y + ((uint64_t)ct * K1 + c) * a.limbs * (uint64_t)M;
     // YDMA: wave-linear LDS destination, swizzle applied on the source side (slot p holds
     // element sw(p)); a group past the batch loads ciphertext 0's rows (in bounds, unused)
@@ -514,7 +591,7 @@ __global__ void __launch_bounds__(Geo<M>::BLOCK) gen_step_kernel(StepArgs a) {
       if constexpr (YDMA) {
         cur = buf + (m & 1) * M;
         wait_vmcnt<0>();
-        poly_sync<M>();
+        lds_sync<TH>();
         if (m + 1 < a.limbs) issue_y(m + 1, buf + ((m + 1) & 1) * M);
       } else if constexpr (PREF) {
 #pragma unroll
@@ -524,12 +601,12 @@ __global__ void __launch_bounds__(Geo<M>::BLOCK) gen_step_kernel(StepArgs a) {
 #pragma unroll
           for (int e = 0; e < VPT; ++e) nx[e] = live ? Yn[tid + e * TH] : cplx{0.0, 0.0};
         }
-        poly_sync<M>();
+        lds_sync<TH>();
       } else {
         const cplx* Ym = Yc + (uint64_t)m * M;
 #pragma unroll
         for (int e = 0; e < VPT; ++e) cur[sw(tid + e * TH)] = live ? Ym[tid + e * TH] : cplx{0.0, 0.0};
-        poly_sync<M>();
+        lds_sync<TH>();
       }
       if constexpr (PP)
         tile_fft<M, TH, true>(cur, W, tid);
@@ -539,15 +616,9 @@ __global__ void __launch_bounds__(Geo<M>::BLOCK) gen_step_kernel(StepArgs a) {
 #pragma unroll
       for (int e = 0; e < VPT; ++e) {
         const int j = tid + e * TH;
-        const cplx z = cmulc(cur[sw(j)], zeta(j));
-        const double tr = z.re + RND_MAGIC, ti = z.im + RND_MAGIC;
-        max_resid = fmax(max_resid, fmax(fabs(z.re - (tr - RND_MAGIC)), fabs(z.im - (ti - RND_MAGIC))));
-        if (sh < 64) {
-          A[e] += ((uint64_t)__double_as_longlong(tr) - RND_MAGIC_BITS) << sh;
-          A[e + VPT] += ((uint64_t)__double_as_longlong(ti) - RND_MAGIC_BITS) << sh;
-        }
+        round_acc(cmulc(cur[sw(j)], zeta(j)), sh, A[e], A[e + VPT], max_resid);
       }
-      poly_sync<M>();
+      lds_sync<TH>();
     }
   }
 
@@ -563,21 +634,17 @@ __global__ void __launch_bounds__(Geo<M>::BLOCK) gen_step_kernel(StepArgs a) {
     uint64_t* accl = reinterpret_cast<uint64_t*>(buf);
 #pragma unroll
     for (int e = 0; e < 2 * VPT; ++e) accl[coef(e)] = A[e];
-    poly_sync<M>();
+    lds_sync<TH>();
     const int nrep = 64 - (int)(a.level * a.base_log);
 #pragma unroll
     for (int e = 0; e < 2 * VPT; ++e) {
-      const uint32_t src = (coef(e) - at) & (2 * N - 1);
-      const uint64_t rv = accl[src & (N - 1)];
-      const uint64_t x = (src < (uint32_t)N ? rv : 0ull - rv) - A[e];
+      const uint64_t x = neg_at<N>(accl, coef(e) - at) - A[e];
       A[e] = nrep > 0 ? decomp_init(x, nrep) : x;  // decomposer state (reuses A)
     }
-    poly_sync<M>();
+    lds_sync<TH>();
     cplx* Xc = a.X + ((uint64_t)ct * K1 + c) * a.level * a.subs * (uint64_t)M;
     const int logB = (int)a.base_log;
-    const int sb = (int)a.bits;
-    const uint64_t half = 1ull << (sb - 1);
-    const uint64_t bmask = (1ull << sb) - 1ull;
+    const SubDigit<uint64_t, true> sub(a.bits, a.subs > 1);
     // STAGE (large M): the twisted sub-digit inputs of all l T transforms go to their X slots
     // first, so no decomposition state is live across the transforms (no register spills at
     // 1024 threads); each slot is then transformed in place through LDS.
@@ -586,19 +653,13 @@ __global__ void __launch_bounds__(Geo<M>::BLOCK) gen_step_kernel(StepArgs a) {
     for (uint32_t q = 0; q < a.level; ++q) {
       int64_t D[2 * VPT];
 #pragma unroll
-      for (int e = 0; e < 2 * VPT; ++e) D[e] = decomp_next64(A[e], logB);
+      for (int e = 0; e < 2 * VPT; ++e) D[e] = decomp_next<uint64_t>(A[e], logB);
 #pragma unroll 1
       for (uint32_t t = 0; t < a.subs; ++t) {
         cplx* dst = Xc + ((uint64_t)q * a.subs + t) * M;
 #pragma unroll
         for (int e = 0; e < VPT; ++e) {
-          int64_t s0 = D[e], s1 = D[e + VPT];
-          if (a.subs > 1) {  // balanced b-bit sub-digit, exact: D - s is a multiple of 2^b
-            s0 = (int64_t)(((uint64_t)D[e] + half) & bmask) - (int64_t)half;
-            s1 = (int64_t)(((uint64_t)D[e + VPT] + half) & bmask) - (int64_t)half;
-            D[e] = (D[e] - s0) >> sb;
-            D[e + VPT] = (D[e + VPT] - s1) >> sb;
-          }
+          const int64_t s0 = sub.take(D[e]), s1 = sub.take(D[e + VPT]);
           const int j = tid + e * TH;
           const cplx z = cmul(cplx{(double)s0, (double)s1}, zeta(j));
           if constexpr (STAGE) {
@@ -608,12 +669,12 @@ __global__ void __launch_bounds__(Geo<M>::BLOCK) gen_step_kernel(StepArgs a) {
           }
         }
         if constexpr (!STAGE) {
-          poly_sync<M>();
+          lds_sync<TH>();
           fwd(buf);
           if (live)
 #pragma unroll
             for (int e = 0; e < VPT; ++e) dst[tid + e * TH] = buf[sw(tid + e * TH)];
-          poly_sync<M>();
+          lds_sync<TH>();
         }
       }
     }
@@ -623,22 +684,18 @@ __global__ void __launch_bounds__(Geo<M>::BLOCK) gen_step_kernel(StepArgs a) {
         cplx* dst = Xc + (uint64_t)x * M;
 #pragma unroll
         for (int e = 0; e < VPT; ++e) buf[sw(tid + e * TH)] = live ? dst[tid + e * TH] : cplx{0.0, 0.0};
-        poly_sync<M>();
+        lds_sync<TH>();
         fwd(buf);
         if (live)
 #pragma unroll
           for (int e = 0; e < VPT; ++e) dst[tid + e * TH] = buf[sw(tid + e * TH)];
-        poly_sync<M>();
+        lds_sync<TH>();
       }
     }
   }
 
-  if constexpr ((MODE & MODE_BACK) != 0) {
-    if (a.resid) {
-      for (int off = 32; off > 0; off >>= 1) max_resid = fmax(max_resid, __shfl_xor(max_resid, off));
-      if ((threadIdx.x & 63) == 0) atomicMax(a.resid, (unsigned long long)__double_as_longlong(max_resid));
-    }
-  }
+  if constexpr ((MODE & MODE_BACK) != 0)
+    if (a.resid) report_resid(max_resid, threadIdx.x & 63, true, a.resid);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -685,44 +742,6 @@ constexpr int ROWLEN = 1024;  // coefficients per row (N / R)
 // frequency held at spectrum position p of the four-step order
 __host__ __device__ constexpr uint32_t big_freq(uint32_t p) {
   return (uint32_t)fft512_freq((int)(p & 63), (int)((p >> 6) & 7)) + 512u * (p >> 9);
-}
-
-// R-point DFT across the rows, natural order in and out (forward exp(-2 pi i jk/R), inverse +)
-constexpr double C16_1 = 0.92387953251128675613, S16_1 = 0.38268343236508977173;  // cos, sin pi/8
-constexpr double R2H = 0.70710678118654752440;
-template <int R, bool INV>
-__device__ __forceinline__ void dft_col(cplx (&u)[R]) {
-  if constexpr (R == 2) {
-    const cplx x0 = u[0], x1 = u[1];
-    u[0] = cadd(x0, x1);
-    u[1] = csub(x0, x1);
-  } else if constexpr (R == 4) {
-    const cplx t0 = cadd(u[0], u[2]), t1 = csub(u[0], u[2]);
-    const cplx t2 = cadd(u[1], u[3]), t3 = mul_mi<INV>(csub(u[1], u[3]));
-    u[0] = cadd(t0, t2);
-    u[2] = csub(t0, t2);
-    u[1] = cadd(t1, t3);
-    u[3] = csub(t1, t3);
-  } else if constexpr (R == 8) {
-    dft8<INV>(u);
-  } else {
-    static_assert(R == 16, "column radix");
-    // even / odd halves, then X[k] = E[k] + w16^k O[k], X[k + 8] = E[k] - w16^k O[k]
-    cplx e[8], o[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) e[i] = u[2 * i], o[i] = u[2 * i + 1];
-    dft8<INV>(e);
-    dft8<INV>(o);
-    const cplx w16[8] = {{1.0, 0.0},     {C16_1, -S16_1}, {R2H, -R2H},     {S16_1, -C16_1},
-                         {0.0, -1.0},    {-S16_1, -C16_1}, {-R2H, -R2H},   {-C16_1, -S16_1}};
-#pragma unroll
-    for (int k = 1; k < 8; ++k) o[k] = k == 4 ? mul_mi<INV>(o[4]) : INV ? cmulc(o[k], w16[k]) : cmul(o[k], w16[k]);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      u[k] = cadd(e[k], o[k]);
-      u[k + 8] = csub(e[k], o[k]);
-    }
-  }
 }
 
 // W32: decomposition state and digits in 32 bits (level * base_log <= 31), else 64
@@ -807,11 +826,8 @@ __global__ void __launch_bounds__(Big<M>::NT) gen_big_step_kernel(StepArgs a) {
 #pragma unroll
     for (int sr = 0; sr < SPW; ++sr)
 #pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const uint32_t src = ((uint32_t)(jrow(sr) + R * jcol(e)) + bt) & (2 * N - 1);
-        const uint64_t v = lut[src & (N - 1)];
-        A[sr][e] = src < (uint32_t)N ? v : 0ull - v;
-      }
+      for (int e = 0; e < 16; ++e)
+        A[sr][e] = neg_at<N>(lut, (uint32_t)(jrow(sr) + R * jcol(e)) + bt);
   } else {
 #pragma unroll
     for (int sr = 0; sr < SPW; ++sr)
@@ -833,16 +849,13 @@ __global__ void __launch_bounds__(Big<M>::NT) gen_big_step_kernel(StepArgs a) {
 #pragma unroll
       for (int p = 0; p < CPT; ++p) {
 #ifndef DG_NOCOL
-        dft_col<R, true>(u[p]);
+        butterfly<R, true>(u[p]);
 #endif
 #pragma unroll
         for (int j1 = 0; j1 < R; ++j1) E[j1 * RS + pos_of(p)] = u[p][j1];
       }
       pair_barrier();
-      // slot shifts stay below 64: the top limb is 64 - (L - 1) b bits wide (key_format), so no
-      // guard (a per-element `sh < 64` test had become one branch per coefficient, with the
-      // accumulator spilled around each)
-      const uint32_t sh = (m * a.bits) & 63u;
+      const uint32_t sh = m * a.bits;
 #pragma unroll
       for (int sr = 0; sr < SPW; ++sr) {
         // row 0 of the wave is read whole before its transform writes the scratch over it
@@ -861,12 +874,7 @@ __global__ void __launch_bounds__(Big<M>::NT) gen_big_step_kernel(StepArgs a) {
         fft512_inv_tw(v, xch, T, lane, gi2, 0);
 #endif
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const double tr = v[e].re + RND_MAGIC, ti = v[e].im + RND_MAGIC;
-          max_resid = fmax(max_resid, fmax(fabs(v[e].re - (tr - RND_MAGIC)), fabs(v[e].im - (ti - RND_MAGIC))));
-          A[sr][e] += ((uint64_t)__double_as_longlong(tr) - RND_MAGIC_BITS) << sh;
-          A[sr][e + 8] += ((uint64_t)__double_as_longlong(ti) - RND_MAGIC_BITS) << sh;
-        }
+        for (int e = 0; e < 8; ++e) round_acc(v[e], sh, A[sr][e], A[sr][e + 8], max_resid);
       }
       pair_barrier();
     }
@@ -876,13 +884,7 @@ __global__ void __launch_bounds__(Big<M>::NT) gen_big_step_kernel(StepArgs a) {
 #pragma unroll
     for (int sr = 0; sr < SPW; ++sr)
 #pragma unroll
-      for (int e = 0; e < 16; ++e) {
-#if GEN_NT_STORES >= 2
-        __builtin_nontemporal_store(A[sr][e], &acc[jrow(sr) * ROWLEN + jcol(e)]);
-#else
-        acc[jrow(sr) * ROWLEN + jcol(e)] = A[sr][e];
-#endif
-      }
+      for (int e = 0; e < 16; ++e) st_once<ST_ALL>(&acc[jrow(sr) * ROWLEN + jcol(e)], A[sr][e]);
   }
 
   if constexpr ((MODE & MODE_FRONT) != 0) {
@@ -900,18 +902,13 @@ __global__ void __launch_bounds__(Big<M>::NT) gen_big_step_kernel(StepArgs a) {
     for (int sr = 0; sr < SPW; ++sr)
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        const uint32_t src = ((uint32_t)(jrow(sr) + R * jcol(e)) - at) & (2 * N - 1);
-        const uint32_t idx = src & (N - 1);
-        const uint64_t rv = accl[(idx & (R - 1)) * ROWLEN + (idx >> LOGR)];
-        const uint64_t x = (src < (uint32_t)N ? rv : 0ull - rv) - A[sr][e];
+        const uint64_t x = neg_at_rows<N, LOGR>(accl, (uint32_t)(jrow(sr) + R * jcol(e)) - at) - A[sr][e];
         S[sr][e] = (St)(nrep > 0 ? decomp_init(x, nrep) : x);
       }
     pair_barrier();
     cplx* Xc = a.X + (uint64_t)poly * a.level * a.subs * M;
-    const int logB = (int)a.base_log, sb = (int)a.bits;
-    // one sub-digit: half = 0 and an all-ones mask make s = D and leave D = 0 (no per-element branch)
-    const bool split = a.subs > 1;
-    const St half = split ? (St)1 << (sb - 1) : (St)0, bmask = split ? ((St)1 << sb) - (St)1 : ~(St)0;
+    const int logB = (int)a.base_log;
+    const SubDigit<St> sub(a.bits, a.subs > 1);
 #ifdef DG_NOFRONT  // timing diagnostic only (wrong results): no forward transforms / X stores
     if (S[0][0] != (St)0x12345) return;
 #endif
@@ -921,10 +918,7 @@ __global__ void __launch_bounds__(Big<M>::NT) gen_big_step_kernel(StepArgs a) {
 #pragma unroll
       for (int sr = 0; sr < SPW; ++sr)
 #pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          if constexpr (W32) D[sr][e] = decomp_next_t<uint32_t>(S[sr][e], logB);
-          else D[sr][e] = decomp_next64(S[sr][e], logB);
-        }
+        for (int e = 0; e < 16; ++e) D[sr][e] = decomp_next<St>(S[sr][e], logB);
 #pragma unroll 1
       for (uint32_t t = 0; t < a.subs; ++t) {
         cplx hold[8];  // SPW = 2: the first row's spectrum, until the second row's transform is done
@@ -933,11 +927,7 @@ __global__ void __launch_bounds__(Big<M>::NT) gen_big_step_kernel(StepArgs a) {
           cplx v[8];
 #pragma unroll
           for (int e = 0; e < 8; ++e) {
-            // balanced b-bit sub-digit, exact: D - s is a multiple of 2^b
-            const Dg s0 = (Dg)(((St)D[sr][e] + half) & bmask) - (Dg)half;
-            const Dg s1 = (Dg)(((St)D[sr][e + 8] + half) & bmask) - (Dg)half;
-            D[sr][e] = (D[sr][e] - s0) >> sb;
-            D[sr][e + 8] = (D[sr][e + 8] - s1) >> sb;
+            const Dg s0 = sub.take(D[sr][e]), s1 = sub.take(D[sr][e + 8]);
             v[e] = {(double)s0, (double)s1};
           }
 #ifndef DG_NOROW
@@ -967,29 +957,20 @@ __global__ void __launch_bounds__(Big<M>::NT) gen_big_step_kernel(StepArgs a) {
 #pragma unroll
           for (int j1 = 0; j1 < R; ++j1) u[j1] = E[j1 * RS + pos_of(p)];
 #ifndef DG_NOCOL
-          dft_col<R, false>(u);
+          butterfly<R, false>(u);
 #endif
 #pragma unroll
-          for (int k1 = 0; k1 < R; ++k1) {
-#if GEN_NT_STORES  // variant: streaming (non-temporal) stores of the spectra the next launch reads
-            __builtin_nontemporal_store(u[k1].re, &dst[k1 * 512 + pos_of(p)].re);
-            __builtin_nontemporal_store(u[k1].im, &dst[k1 * 512 + pos_of(p)].im);
-#else
-            dst[k1 * 512 + pos_of(p)] = u[k1];
-#endif
-          }
+          for (int k1 = 0; k1 < R; ++k1) st_once<ST_XY>(&dst[k1 * 512 + pos_of(p)], u[k1]);
         }
         pair_barrier();
       }
     }
   }
 
-  if constexpr ((MODE & MODE_BACK) != 0) {
-    if (a.resid) {
-      for (int off = 32; off > 0; off >>= 1) max_resid = fmax(max_resid, __shfl_xor(max_resid, off));
-      if (lane == 0) atomicMax(a.resid, (unsigned long long)__double_as_longlong(max_resid));
-    }
-  }
+  // (only with a sink: the shuffle rounds of report_resid at the end of every step launch, one
+  // workgroup per CU with nothing to hide them, measured -0.9 % at N = 8192)
+  if constexpr ((MODE & MODE_BACK) != 0)
+    if (a.resid) report_resid(max_resid, lane, true, a.resid);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1067,9 +1048,7 @@ __global__ void __launch_bounds__(256) gen_split_init_kernel(SplitArgs a) {
     const uint64_t row = a.in_idx ? a.in_idx[s] : s;
     const uint32_t bt = modswitch(a.in[row * (uint64_t)(a.n + 1) + a.n], LOG2_2N);
     const uint64_t* lut = a.luts + (a.lut_idx ? a.lut_idx[s] : 0ull) * (uint64_t)(K1 * N) + (uint64_t)c * N;
-    const uint32_t src = (nn + bt) & (2 * N - 1);
-    const uint64_t v = lut[src & (N - 1)];
-    a.acc[poly * N + (uint64_t)(nn & (G::R - 1)) * (N / G::R) + (nn >> G::LOGR)] = src < (uint32_t)N ? v : 0ull - v;
+    a.acc[poly * N + (uint64_t)(nn & (G::R - 1)) * (N / G::R) + (nn >> G::LOGR)] = neg_at<N>(lut, nn + bt);
   }
 }
 
@@ -1130,26 +1109,20 @@ __global__ void __launch_bounds__(512) gen_split_front_kernel(SplitArgs a) {
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       const uint32_t nn = (uint32_t)(q.jg(sr) + R * jcol(e));
-      const uint32_t src = (nn - at) & (2 * N - 1), idx = src & (N - 1);
-      const uint64_t rv = acc[(uint64_t)(idx & (R - 1)) * ROWLEN + (idx >> G::LOGR)];
-      const uint64_t x = (src < (uint32_t)N ? rv : 0ull - rv) - acc[(uint64_t)q.jg(sr) * ROWLEN + jcol(e)];
+      const uint64_t x = neg_at_rows<N, G::LOGR>(acc, nn - at) - acc[(uint64_t)q.jg(sr) * ROWLEN + jcol(e)];
       Sx[sr][e] = (St)(nrep > 0 ? decomp_init(x, nrep) : x);
     }
   pair_barrier();  // fft512 tables, beta
   cplx* Xc = a.X + (uint64_t)poly * a.level * a.subs * S * (SPLIT_ROWS * 512) + (uint64_t)h * SPLIT_ROWS * 512;
-  const int logB = (int)a.base_log, sb = (int)a.bits;
-  const bool split = a.subs > 1;
-  const St half = split ? (St)1 << (sb - 1) : (St)0, bmask = split ? ((St)1 << sb) - (St)1 : ~(St)0;
+  const int logB = (int)a.base_log;
+  const SubDigit<St> sub(a.bits, a.subs > 1);
 #pragma unroll 1
   for (uint32_t qq = 0; qq < a.level; ++qq) {
     Dg D[2][16];
 #pragma unroll
     for (int sr = 0; sr < 2; ++sr)
 #pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        if constexpr (W32) D[sr][e] = decomp_next_t<uint32_t>(Sx[sr][e], logB);
-        else D[sr][e] = decomp_next64(Sx[sr][e], logB);
-      }
+      for (int e = 0; e < 16; ++e) D[sr][e] = decomp_next<St>(Sx[sr][e], logB);
 #pragma unroll 1
     for (uint32_t t = 0; t < a.subs; ++t) {
       cplx hold[8];  // the first row's spectrum, until the second row's transform is done
@@ -1158,10 +1131,7 @@ __global__ void __launch_bounds__(512) gen_split_front_kernel(SplitArgs a) {
         cplx v[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-          const Dg s0 = (Dg)(((St)D[sr][e] + half) & bmask) - (Dg)half;
-          const Dg s1 = (Dg)(((St)D[sr][e + 8] + half) & bmask) - (Dg)half;
-          D[sr][e] = (D[sr][e] - s0) >> sb;
-          D[sr][e + 8] = (D[sr][e + 8] - s1) >> sb;
+          const Dg s0 = sub.take(D[sr][e]), s1 = sub.take(D[sr][e + 8]);
           v[e] = {(double)s0, (double)s1};
         }
         fft512_fwd(v, xch, q.T, lane);
@@ -1185,16 +1155,9 @@ __global__ void __launch_bounds__(512) gen_split_front_kernel(SplitArgs a) {
       cplx u[SPLIT_ROWS];
 #pragma unroll
       for (int jl = 0; jl < SPLIT_ROWS; ++jl) u[jl] = q.E[jl * RS + pos];
-      dft_col<SPLIT_ROWS, false>(u);
+      butterfly<SPLIT_ROWS, false>(u);
 #pragma unroll
-      for (int k1 = 0; k1 < SPLIT_ROWS; ++k1) {
-#if GEN_NT_STORES >= 2
-        __builtin_nontemporal_store(u[k1].re, &dst[k1 * 512 + pos].re);
-        __builtin_nontemporal_store(u[k1].im, &dst[k1 * 512 + pos].im);
-#else
-        dst[k1 * 512 + pos] = u[k1];
-#endif
-      }
+      for (int k1 = 0; k1 < SPLIT_ROWS; ++k1) st_once<ST_ALL>(&dst[k1 * 512 + pos], u[k1]);
       pair_barrier();
     }
   }
@@ -1268,12 +1231,12 @@ __global__ void __launch_bounds__(512) gen_split_back_kernel(SplitArgs a) {
         u[k1] = hsum;
       }
     }
-    dft_col<SPLIT_ROWS, true>(u);
+    butterfly<SPLIT_ROWS, true>(u);
 #pragma unroll
     for (int jl = 0; jl < SPLIT_ROWS; ++jl) q.E[jl * RS + pos] = u[jl];
     if (LATE && m + 1 < a.limbs) load_h(m + 1, 0, NPF);
     pair_barrier();
-    const uint32_t sh = (m * a.bits) & 63u;
+    const uint32_t sh = m * a.bits;
 #pragma unroll
     for (int sr = 0; sr < 2; ++sr) {
       // row 0 of the wave is read whole before its transform writes the scratch over it
@@ -1288,29 +1251,15 @@ __global__ void __launch_bounds__(512) gen_split_back_kernel(SplitArgs a) {
       inv_p2_stage_tw(gi2, q.T, lane & 7);
       fft512_inv_tw(v, xch, q.T, lane, gi2, 0);
 #pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const double tr = v[e].re + RND_MAGIC, ti = v[e].im + RND_MAGIC;
-        max_resid = fmax(max_resid, fmax(fabs(v[e].re - (tr - RND_MAGIC)), fabs(v[e].im - (ti - RND_MAGIC))));
-        A[sr][e] += ((uint64_t)__double_as_longlong(tr) - RND_MAGIC_BITS) << sh;
-        A[sr][e + 8] += ((uint64_t)__double_as_longlong(ti) - RND_MAGIC_BITS) << sh;
-      }
+      for (int e = 0; e < 8; ++e) round_acc(v[e], sh, A[sr][e], A[sr][e + 8], max_resid);
     }
     pair_barrier();
   }
 #pragma unroll
   for (int sr = 0; sr < 2; ++sr)
 #pragma unroll
-    for (int e = 0; e < 16; ++e) {
-#if GEN_NT_STORES >= 2
-      __builtin_nontemporal_store(A[sr][e], &acc[(uint64_t)q.jg(sr) * ROWLEN + jcol(e)]);
-#else
-      acc[(uint64_t)q.jg(sr) * ROWLEN + jcol(e)] = A[sr][e];
-#endif
-    }
-  if (a.resid) {
-    for (int off = 32; off > 0; off >>= 1) max_resid = fmax(max_resid, __shfl_xor(max_resid, off));
-    if (lane == 0) atomicMax(a.resid, (unsigned long long)__double_as_longlong(max_resid));
-  }
+    for (int e = 0; e < 16; ++e) st_once<ST_ALL>(&acc[(uint64_t)q.jg(sr) * ROWLEN + jcol(e)], A[sr][e]);
+  if (a.resid) report_resid(max_resid, lane, true, a.resid);
 }
 
 // Y[ct][c][m][p] = sum over (r, q, t) with 0 <= m - t < L of X_p[r][q][t] G_i[c][m-t][r][q][p], with
@@ -1397,12 +1346,7 @@ __global__ void __launch_bounds__(256) gen_mac_split_kernel(MacSplitArgs a) {
       cplx hsum = {0.0, 0.0};
 #pragma unroll
       for (int uu = 0; uu < S; ++uu) hsum = cadd(hsum, cmulc(from(y, uu), wi[uu]));
-#if GEN_NT_STORES >= 2
-      __builtin_nontemporal_store(hsum.re, &Hct[(uint64_t)m * M].re);
-      __builtin_nontemporal_store(hsum.im, &Hct[(uint64_t)m * M].im);
-#else
-      Hct[(uint64_t)m * M] = hsum;
-#endif
+      st_once<ST_ALL>(&Hct[(uint64_t)m * M], hsum);
     }
   }
 }
@@ -1494,12 +1438,8 @@ __global__ void __launch_bounds__(512) gen_split_convert_kernel(SplitConvArgs a)
       for (int z = 0; z < 2; ++z) {
         uint64_t gv = g[(uint64_t)(q.jg(sr) + R * jcol(e + 8 * z))];
         int64_t s0 = 0;
-        for (uint32_t j = 0; j <= lim; ++j) {
-          const uint32_t w = j + 1 < a.limbs ? a.bits : 64 - (a.limbs - 1) * a.bits;
-          const uint64_t half = 1ull << (w - 1), bmask = (1ull << w) - 1ull;
-          s0 = (int64_t)((gv + half) & bmask) - (int64_t)half;
-          gv = (gv - (uint64_t)s0) >> a.bits;
-        }
+        for (uint32_t j = 0; j <= lim; ++j)
+          s0 = SubDigit<uint64_t>(j + 1 < a.limbs ? a.bits : 64 - (a.limbs - 1) * a.bits, true).take(gv);
         sv[z] = s0;
       }
       v[e] = {(double)sv[0], (double)sv[1]};
@@ -1523,7 +1463,7 @@ __global__ void __launch_bounds__(512) gen_split_convert_kernel(SplitConvArgs a)
   cplx u[SPLIT_ROWS];
 #pragma unroll
   for (int jl = 0; jl < SPLIT_ROWS; ++jl) u[jl] = q.E[jl * RS + pos];
-  dft_col<SPLIT_ROWS, false>(u);
+  butterfly<SPLIT_ROWS, false>(u);
   cplx* dst = a.Gs + ((uint64_t)item * S + h) * SPLIT_ROWS * 512;
 #pragma unroll
   for (int k1 = 0; k1 < SPLIT_ROWS; ++k1) dst[k1 * 512 + pos] = u[k1];
@@ -1645,15 +1585,12 @@ __global__ void __launch_bounds__(512) gen_fused_kernel(FusedArgs a) {
     const uint32_t bt = modswitch(lwe[a.n], LOG2_2N);
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-      const uint32_t src = ((uint32_t)(j1 + R * jcol(e)) + bt) & (2 * N - 1);
-      const uint64_t v = lut[src & (N - 1)];
-      A[e] = src < (uint32_t)N ? v : 0ull - v;
+      A[e] = neg_at<N>(lut, (uint32_t)(j1 + R * jcol(e)) + bt);
     }
   }
-  const int logB = (int)a.base_log, sb = (int)a.bits;
+  const int logB = (int)a.base_log;
   const int nrep = 64 - LV * logB;
-  const bool split = T > 1;
-  const St half = split ? (St)1 << (sb - 1) : (St)0, bmask = split ? ((St)1 << sb) - (St)1 : ~(St)0;
+  const SubDigit<St> sub(a.bits, T > 1);
   double max_resid = 0.0;
   pair_barrier();  // tables, tau
 
@@ -1668,10 +1605,7 @@ __global__ void __launch_bounds__(512) gen_fused_kernel(FusedArgs a) {
     St S[16];
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-      const uint32_t src = ((uint32_t)(j1 + R * jcol(e)) - at) & (2 * N - 1);
-      const uint32_t idx = src & (N - 1);
-      const uint64_t rv = accl[c * N + (idx & (R - 1)) * (N / R) + (idx >> LOGR)];
-      const uint64_t x = (src < (uint32_t)N ? rv : 0ull - rv) - A[e];
+      const uint64_t x = neg_at_rows<N, LOGR>(accl + c * N, (uint32_t)(j1 + R * jcol(e)) - at) - A[e];
       S[e] = (St)(nrep > 0 ? decomp_init(x, nrep) : x);
     }
     pair_barrier();  // the rows are free again
@@ -1680,20 +1614,13 @@ __global__ void __launch_bounds__(512) gen_fused_kernel(FusedArgs a) {
     for (int q = 0; q < LV; ++q) {
       Dg D[16];
 #pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        if constexpr (W32) D[e] = decomp_next_t<uint32_t>(S[e], logB);
-        else D[e] = decomp_next64(S[e], logB);
-      }
+      for (int e = 0; e < 16; ++e) D[e] = decomp_next<St>(S[e], logB);
 #pragma unroll
       for (int t = 0; t < T; ++t) {
         cplx v[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-          // balanced b-bit sub-digit, exact: D - s is a multiple of 2^b
-          const Dg s0 = (Dg)(((St)D[e] + half) & bmask) - (Dg)half;
-          const Dg s1 = (Dg)(((St)D[e + 8] + half) & bmask) - (Dg)half;
-          D[e] = (D[e] - s0) >> sb;
-          D[e + 8] = (D[e + 8] - s1) >> sb;
+          const Dg s0 = sub.take(D[e]), s1 = sub.take(D[e + 8]);
           v[e] = {(double)s0, (double)s1};
         }
         fft512_fwd(v, row, TB, lane);
@@ -1708,7 +1635,7 @@ __global__ void __launch_bounds__(512) gen_fused_kernel(FusedArgs a) {
           cplx u[R];
 #pragma unroll
           for (int jj = 0; jj < R; ++jj) u[jj] = E[(r * R + jj) * RS + pos];
-          dft_col<R, false>(u);
+          butterfly<R, false>(u);
 #pragma unroll
           for (int k1 = 0; k1 < R; ++k1) X[(r * LV + q) * T + t][k1] = u[k1];
         }
@@ -1756,7 +1683,7 @@ __global__ void __launch_bounds__(512) gen_fused_kernel(FusedArgs a) {
               }
             }
         }
-        dft_col<R, true>(y);
+        butterfly<R, true>(y);
 #pragma unroll
         for (int jj = 0; jj < R; ++jj) E[(cc * R + jj) * RS + pos] = y[jj];
       }
@@ -1772,15 +1699,9 @@ __global__ void __launch_bounds__(512) gen_fused_kernel(FusedArgs a) {
       cplx gi2[4];
       inv_p2_stage_tw(gi2, TB, lane & 7);
       fft512_inv_tw(v, row, TB, lane, gi2, 0);
-      // slot shifts stay below 64: the top limb is 64 - (L - 1) b bits wide (key_format)
-      const uint32_t sh = ((uint32_t)m * a.bits) & 63u;
+      const uint32_t sh = (uint32_t)m * a.bits;
 #pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const double tr = v[e].re + RND_MAGIC, ti = v[e].im + RND_MAGIC;
-        max_resid = fmax(max_resid, fmax(fabs(v[e].re - (tr - RND_MAGIC)), fabs(v[e].im - (ti - RND_MAGIC))));
-        A[e] += ((uint64_t)__double_as_longlong(tr) - RND_MAGIC_BITS) << sh;
-        A[e + 8] += ((uint64_t)__double_as_longlong(ti) - RND_MAGIC_BITS) << sh;
-      }
+      for (int e = 0; e < 8; ++e) round_acc(v[e], sh, A[e], A[e + 8], max_resid);
       pair_barrier();  // the rows are written by the next slot's column DFTs
     }
   }
@@ -1796,10 +1717,7 @@ __global__ void __launch_bounds__(512) gen_fused_kernel(FusedArgs a) {
     else if (j == 0)
       o[N] = A[e];
   }
-  if (a.resid) {
-    for (int off = 32; off > 0; off >>= 1) max_resid = fmax(max_resid, __shfl_xor(max_resid, off));
-    if (lane == 0) atomicMax(a.resid, (unsigned long long)__double_as_longlong(max_resid));
-  }
+  report_resid(max_resid, lane, true, a.resid);  // once per bootstrap: no test around it (see gen_coop_kernel)
 }
 
 
@@ -1915,15 +1833,12 @@ __global__ void __launch_bounds__(512) gen_coop_kernel(CoopArgs a) {
     const uint32_t bt = modswitch(lwe[a.n], LOG2_2N);
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-      const uint32_t src = ((uint32_t)(j1 + R * jcol(e)) + bt) & (2 * N - 1);
-      const uint64_t v = lut[src & (N - 1)];
-      A[e] = src < (uint32_t)N ? v : 0ull - v;
+      A[e] = neg_at<N>(lut, (uint32_t)(j1 + R * jcol(e)) + bt);
     }
   }
-  const int logB = (int)a.base_log, sb = (int)a.bits;
+  const int logB = (int)a.base_log;
   const int nrep = 64 - LV * logB;
-  const bool split = T > 1;
-  const St half = split ? (St)1 << (sb - 1) : (St)0, bmask = split ? ((St)1 << sb) - (St)1 : ~(St)0;
+  const SubDigit<St> sub(a.bits, T > 1);
   double max_resid = 0.0;
 
   // ---- hand-off endpoints (byte offsets: per-lane voffset of the sc1 buffer accesses)
@@ -1971,10 +1886,7 @@ __global__ void __launch_bounds__(512) gen_coop_kernel(CoopArgs a) {
     St S[16];
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-      const uint32_t src = ((uint32_t)(j1 + R * jcol(e)) - at) & (2 * N - 1);
-      const uint32_t idx = src & (N - 1);
-      const uint64_t rv = accl[(idx & (R - 1)) * (N / R) + (idx >> LOGR)];
-      const uint64_t x = (src < (uint32_t)N ? rv : 0ull - rv) - A[e];
+      const uint64_t x = neg_at_rows<N, LOGR>(accl, (uint32_t)(j1 + R * jcol(e)) - at) - A[e];
       S[e] = (St)(nrep > 0 ? decomp_init(x, nrep) : x);
     }
     pair_barrier();  // the rows are free again
@@ -1984,19 +1896,13 @@ __global__ void __launch_bounds__(512) gen_coop_kernel(CoopArgs a) {
     for (int q = 0; q < LV; ++q) {
       Dg D[16];
 #pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        if constexpr (W32) D[e] = decomp_next_t<uint32_t>(S[e], logB);
-        else D[e] = decomp_next64(S[e], logB);
-      }
+      for (int e = 0; e < 16; ++e) D[e] = decomp_next<St>(S[e], logB);
 #pragma unroll
       for (int t = 0; t < T; ++t) {
         cplx v[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-          const Dg s0 = (Dg)(((St)D[e] + half) & bmask) - (Dg)half;
-          const Dg s1 = (Dg)(((St)D[e + 8] + half) & bmask) - (Dg)half;
-          D[e] = (D[e] - s0) >> sb;
-          D[e + 8] = (D[e + 8] - s1) >> sb;
+          const Dg s0 = sub.take(D[e]), s1 = sub.take(D[e + 8]);
           v[e] = {(double)s0, (double)s1};
         }
         fft512_fwd(v, row, TB, lane);
@@ -2009,7 +1915,7 @@ __global__ void __launch_bounds__(512) gen_coop_kernel(CoopArgs a) {
         cplx u[R];
 #pragma unroll
         for (int jj = 0; jj < R; ++jj) u[jj] = E[jj * RS + pos];
-        dft_col<R, false>(u);
+        butterfly<R, false>(u);
         const int s = q * T + t;
         // (uniform branches: a select on c would become an indexed, scratch-backed array)
         auto keep_send = [&](auto CC) __attribute__((always_inline)) {
@@ -2123,7 +2029,7 @@ __global__ void __launch_bounds__(512) gen_coop_kernel(CoopArgs a) {
       };
       if (c) gather(std::integral_constant<int, 1>{});
       else gather(std::integral_constant<int, 0>{});
-      dft_col<R, true>(u);
+      butterfly<R, true>(u);
 #pragma unroll
       for (int jj = 0; jj < R; ++jj) E[jj * RS + pos] = u[jj];
       pair_barrier();
@@ -2137,14 +2043,9 @@ __global__ void __launch_bounds__(512) gen_coop_kernel(CoopArgs a) {
       cplx gi2[4];
       inv_p2_stage_tw(gi2, TB, lane & 7);
       fft512_inv_tw(v, row, TB, lane, gi2, 0);
-      const uint32_t sh = ((uint32_t)m * a.bits) & 63u;
+      const uint32_t sh = (uint32_t)m * a.bits;
 #pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const double tr = v[e].re + RND_MAGIC, ti = v[e].im + RND_MAGIC;
-        max_resid = fmax(max_resid, fmax(fabs(v[e].re - (tr - RND_MAGIC)), fabs(v[e].im - (ti - RND_MAGIC))));
-        A[e] += ((uint64_t)__double_as_longlong(tr) - RND_MAGIC_BITS) << sh;
-        A[e + 8] += ((uint64_t)__double_as_longlong(ti) - RND_MAGIC_BITS) << sh;
-      }
+      for (int e = 0; e < 8; ++e) round_acc(v[e], sh, A[e], A[e + 8], max_resid);
       pair_barrier();  // the rows are written by the next slot's column DFTs
     }
   }
@@ -2160,10 +2061,9 @@ __global__ void __launch_bounds__(512) gen_coop_kernel(CoopArgs a) {
     else if (j == 0)
       o[N] = A[e];
   }
-  if (a.resid) {
-    for (int off = 32; off > 0; off >>= 1) max_resid = fmax(max_resid, __shfl_xor(max_resid, off));
-    if (lane == 0) atomicMax(a.resid, (unsigned long long)__double_as_longlong(max_resid));
-  }
+  // (no `if (a.resid)` around it: with the test the compiler lays out the hand-off polling loops
+  // differently, measured -2.2 % at opt7; the tail runs once per bootstrap)
+  report_resid(max_resid, lane, true, a.resid);
 }
 
 // Y[ct][c][m][f] = sum over (r, q, t) with 0 <= m - t < L of X[ct][r][q][t][f] * G_i[c][m-t][r][q][f]
@@ -2296,12 +2196,7 @@ __global__ void __launch_bounds__(256) gen_mac2k1_kernel(MacArgs a) {
             y.im = __builtin_fma(xg.re, g.im, __builtin_fma(xg.im, g.re, y.im));
           }
         }
-        #if GEN_NT_STORES
-        __builtin_nontemporal_store(y.re, &Yct[(uint64_t)m * M].re);
-        __builtin_nontemporal_store(y.im, &Yct[(uint64_t)m * M].im);
-#else
-        Yct[(uint64_t)m * M] = y;
-#endif
+        st_once<ST_XY>(&Yct[(uint64_t)m * M], y);
       }
     }
   }
@@ -2399,15 +2294,13 @@ __global__ void __launch_bounds__((TileGeo<M, K1, KL, T, L, C>::NT)) gen_tile_ke
     const uint32_t bt = live ? modswitch(lwe[a.n], LOG2_2N) : 0u;
 #pragma unroll
     for (int e = 0; e < 2 * VPT; ++e) {
-      const uint32_t src = (coef(e) + bt) & (2 * N - 1);
-      const uint64_t v = live ? lut[src & (N - 1)] : 0ull;
-      A[e] = src < (uint32_t)N ? v : 0ull - v;
+      A[e] = live ? neg_at<N>(lut, coef(e) + bt) : 0ull;
     }
   }
   __syncthreads();
-  const int logB = (int)a.base_log, sb = (int)a.bits;
+  const int logB = (int)a.base_log;
   const int nrep = 64 - LV * logB;
-  const uint64_t half = 1ull << (sb - 1), bmask = (1ull << sb) - 1ull;
+  const SubDigit<uint64_t> sub(a.bits, T > 1);
   // key values of product item (c, f) = (it / M, it % M), it = threadIdx.x + s NT, for slot m
   // Output-group items (PAIR): an item = (frequency, CP output polynomials, C / LCS ciphertexts
   // of the tile), so each digit-spectrum value read from LDS serves CP outputs (the product
@@ -2454,36 +2347,28 @@ __global__ void __launch_bounds__((TileGeo<M, K1, KL, T, L, C>::NT)) gen_tile_ke
     uint64_t* rot = reinterpret_cast<uint64_t*>(ybuf);
 #pragma unroll
     for (int e = 0; e < 2 * VPT; ++e) rot[coef(e)] = A[e];
-    tile_sync<TH>();
+    lds_sync<TH>();
     uint64_t S[2 * VPT];
 #pragma unroll
     for (int e = 0; e < 2 * VPT; ++e) {
-      const uint32_t src = (coef(e) - at) & (2 * N - 1);
-      const uint64_t rv = rot[src & (N - 1)];
-      const uint64_t x = (src < (uint32_t)N ? rv : 0ull - rv) - A[e];
+      const uint64_t x = neg_at<N>(rot, coef(e) - at) - A[e];
       S[e] = nrep > 0 ? decomp_init(x, nrep) : x;
     }
 #pragma unroll 1
     for (int q = 0; q < LV; ++q) {
       int64_t D[2 * VPT];
 #pragma unroll
-      for (int e = 0; e < 2 * VPT; ++e) D[e] = decomp_next64(S[e], logB);
+      for (int e = 0; e < 2 * VPT; ++e) D[e] = decomp_next<uint64_t>(S[e], logB);
 #pragma unroll
       for (int t = 0; t < T; ++t) {
         cplx* xs = Xs + ((lct * KL + c * LV + q) * T + t) * M;
 #pragma unroll
         for (int e = 0; e < VPT; ++e) {
-          int64_t s0 = D[e], s1 = D[e + VPT];
-          if constexpr (T > 1) {
-            s0 = (int64_t)(((uint64_t)D[e] + half) & bmask) - (int64_t)half;
-            s1 = (int64_t)(((uint64_t)D[e + VPT] + half) & bmask) - (int64_t)half;
-            D[e] = (D[e] - s0) >> sb;
-            D[e + VPT] = (D[e + VPT] - s1) >> sb;
-          }
+          const int64_t s0 = sub.take(D[e]), s1 = sub.take(D[e + VPT]);
           const int j = tid + e * TH;
           xs[sw(j)] = cmul(cplx{(double)s0, (double)s1}, zeta(j));
         }
-        tile_sync<TH>();
+        lds_sync<TH>();
         tile_fft<M, TH, false>(xs, W, tid);
       }
     }
@@ -2649,13 +2534,7 @@ __global__ void __launch_bounds__((TileGeo<M, K1, KL, T, L, C>::NT)) gen_tile_ke
 #pragma unroll
       for (int e = 0; e < VPT; ++e) {
         const int j = tid + e * TH;
-        const cplx z = cmulc(ybuf[sw(j)], zeta(j));
-        const double tr = z.re + RND_MAGIC, ti = z.im + RND_MAGIC;
-        max_resid = fmax(max_resid, fmax(fabs(z.re - (tr - RND_MAGIC)), fabs(z.im - (ti - RND_MAGIC))));
-        if (sh < 64) {
-          A[e] += ((uint64_t)__double_as_longlong(tr) - RND_MAGIC_BITS) << sh;
-          A[e + VPT] += ((uint64_t)__double_as_longlong(ti) - RND_MAGIC_BITS) << sh;
-        }
+        round_acc(cmulc(ybuf[sw(j)], zeta(j)), sh, A[e], A[e + VPT], max_resid);
       }
       __syncthreads();
     }
@@ -2673,10 +2552,7 @@ __global__ void __launch_bounds__((TileGeo<M, K1, KL, T, L, C>::NT)) gen_tile_ke
         o[(uint64_t)(K1 - 1) * N] = A[e];
     }
   }
-  if (a.resid) {
-    for (int off = 32; off > 0; off >>= 1) max_resid = fmax(max_resid, __shfl_xor(max_resid, off));
-    if ((threadIdx.x & 63) == 0) atomicMax(a.resid, (unsigned long long)__double_as_longlong(max_resid));
-  }
+  if (a.resid) report_resid(max_resid, threadIdx.x & 63, true, a.resid);
 }
 
 // sample extract (nth = 0): out[r N + 0] = A_r[0], out[r N + j] = -A_r[N - j], out[k N] = B[0].
@@ -2743,15 +2619,11 @@ __global__ void __launch_bounds__(Geo<M>::THREADS) gen_convert_kernel(cplx* G, c
   for (uint32_t lim = 0; lim < limbs; ++lim) {
     // balanced limbs: g = sum_j 2^{jb} g_j mod 2^64, |g_j| <= 2^(b-1); the top limb only matters
     // mod 2^(64 - (L-1) b), so it is balanced in that width (no DC offset in its spectrum)
-    const uint32_t w = lim + 1 < limbs ? bits : 64 - (limbs - 1) * bits;
-    const uint64_t half = 1ull << (w - 1);
-    const uint64_t bmask = (1ull << w) - 1ull;
+    // (take() shifts the top limb out by its own width; nothing is read after it)
+    const SubDigit<uint64_t> sub(lim + 1 < limbs ? bits : 64 - (limbs - 1) * bits, true);
 #pragma unroll
     for (int e = 0; e < VPT; ++e) {
-      const int64_t s0 = (int64_t)((gv[e] + half) & bmask) - (int64_t)half;
-      const int64_t s1 = (int64_t)((gv[e + VPT] + half) & bmask) - (int64_t)half;
-      gv[e] = (gv[e] - (uint64_t)s0) >> bits;
-      gv[e + VPT] = (gv[e + VPT] - (uint64_t)s1) >> bits;
+      const int64_t s0 = sub.take(gv[e]), s1 = sub.take(gv[e + VPT]);
       const int j = tid + e * TH;
       buf[sw(j)] = cmul(cplx{(double)s0, (double)s1}, Z[j]);
     }
@@ -2846,6 +2718,24 @@ static Tables tables_for(uint32_t N) {
   return t;
 }
 
+// the error tail of every launch path: 0, or -1 with "generic <what> launch failed: ..." set
+static int launch_ok(const char* what) {
+  const hipError_t e = hipGetLastError();
+  if (e == hipSuccess) return 0;
+  set_error("generic %s launch failed: %s", what, hipGetErrorString(e));
+  return -1;
+}
+
+// decomposition state and digits in 32 bits (the kernels' W32), computed in 64
+static bool narrow_state(uint32_t level, uint32_t base_log) { return (uint64_t)level * base_log <= 31; }
+
+// a positive integer knob of the environment, read per call (tests and A/B runs change them between
+// calls); dflt when unset or not positive
+static uint64_t env_knob(const char* name, uint64_t dflt) {
+  const char* e = getenv(name);
+  return e && atoi(e) > 0 ? (uint64_t)atoi(e) : dflt;
+}
+
 template <int M, int MODE>
 static void launch_step(const StepArgs& s, uint32_t K1, hipStream_t st) {
   const uint64_t polys = (uint64_t)s.count * K1;
@@ -2856,7 +2746,7 @@ static void launch_step(const StepArgs& s, uint32_t K1, hipStream_t st) {
 template <int M, int MODE>
 static void launch_big_step(const StepArgs& s, uint32_t K1, hipStream_t st) {
   const uint32_t blocks = s.count * K1;  // one workgroup per polynomial
-  if (s.level * s.base_log <= 31)
+  if (narrow_state(s.level, s.base_log))
     hipLaunchKernelGGL((gen_big_step_kernel<M, MODE, true>), dim3(blocks), dim3(Big<M>::NT), 0, st, s);
   else
     hipLaunchKernelGGL((gen_big_step_kernel<M, MODE, false>), dim3(blocks), dim3(Big<M>::NT), 0, st, s);
@@ -2926,7 +2816,7 @@ static bool fused_dispatch(const FusedArgs& f, uint32_t k, uint32_t N, uint32_t 
                            hipStream_t st) {
   const char* fe = getenv("CONCRETE_HIP_GEN_FUSED");  // read per call (tests cover both paths)
   if ((fe && atoi(fe) == 0) || k != 1 || !four_step(N)) return false;
-  const bool w32 = (uint64_t)level * f.base_log <= 31;
+  const bool w32 = narrow_state(level, f.base_log);
   if (N != 4096) return false;
 #define GEN_FUSED(LVv, Tv, Lv)                                                                               \
   if (level == LVv && T == Tv && L == Lv) {                                                                  \
@@ -2948,7 +2838,7 @@ static bool fused_dispatch(const FusedArgs& f, uint32_t k, uint32_t N, uint32_t 
 static bool coop_dispatch(const PbsArgs& a, const Tables& tb, uint32_t T, uint32_t L, uint32_t b, int* rc) {
   const char* ce = getenv("CONCRETE_HIP_GEN_COOP");  // read per call (tests cover both paths)
   if ((ce && atoi(ce) == 0) || a.k != 1 || a.N != 8192 || !four_step(a.N)) return false;
-  const bool w32 = (uint64_t)a.level * a.base_log <= 31;
+  const bool w32 = narrow_state(a.level, a.base_log);
   void (*kern)(CoopArgs) = nullptr;
 #define GEN_COOP(LVv, Tv, Lv)                                                                    \
   if (a.level == LVv && T == Tv && L == Lv) kern = w32 ? gen_coop_kernel<LVv, Tv, Lv, true> : gen_coop_kernel<LVv, Tv, Lv, false>;
@@ -2956,10 +2846,9 @@ static bool coop_dispatch(const PbsArgs& a, const Tables& tb, uint32_t T, uint32
 #undef GEN_COOP
   if (!kern) return false;
   const uint64_t xb_ct = 2ull * a.level * T * 4 * 512 * sizeof(cplx), yb_ct = 2ull * 2 * 4 * 512 * sizeof(cplx);
-  const char* ke = getenv("CONCRETE_HIP_GEN_CHUNK");
   // (<= 8192 ciphertexts per launch: the kernel's hand-off buffer descriptors count bytes in 31 bits)
-  const uint32_t chunk = (uint32_t)std::min<uint64_t>(
-      a.num_samples, std::min<uint64_t>(ke && atoi(ke) > 0 ? (uint64_t)atoi(ke) : 4096, 8192));
+  const uint32_t chunk =
+      (uint32_t)std::min<uint64_t>(a.num_samples, std::min<uint64_t>(env_knob("CONCRETE_HIP_GEN_CHUNK", 4096), 8192));
   const uint64_t flag_bytes = ((2ull * chunk + 1) * 4 + 15) / 16 * 16;
   char* scratch = nullptr;
   keep_pool_memory();
@@ -2975,20 +2864,98 @@ static bool coop_dispatch(const PbsArgs& a, const Tables& tb, uint32_t T, uint32
                       tb.Tau, a.resid, xb, yb, flags, a.guard.status, a.guard.spin_limit, base, cnt, a.n, a.base_log,
                       b, (uint32_t)(xb_ct * cnt), (uint32_t)(yb_ct * cnt)};
     hipLaunchKernelGGL(kern, dim3(2 * cnt), dim3(512), 0, a.stream, ca);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-      set_error("generic pbs (coop) launch failed: %s", hipGetErrorString(e));
-      *rc = -1;
-      break;
-    }
+    if ((*rc = launch_ok("pbs (coop)")) != 0) break;
   }
   CHIP_CHECK(hipFreeAsync(scratch, a.stream));
   return true;
 }
 
-// N >= 32768: the split path (S = N / 16384 workgroups per polynomial), one stream, chunks of
-// <= 2 GB of scratch run one after another: init, then per CMUX step the product, the back half
-// and the next step's front half.
+// ------------------------------------------------------------------------------------------
+// The chunk driver of the two-launch and split paths.  A call runs in chunks of <= 2 GB of X / Y /
+// accumulator scratch (CONCRETE_HIP_GEN_BUDGET_MB), capped at CONCRETE_HIP_GEN_CHUNK ciphertexts
+// (tests: several chunks at small batches).  With two or more chunks, groups of NS chunks run on NS
+// streams (the caller's and library streams of the device; CONCRETE_HIP_GEN_STREAMS = 1..4, default
+// 2), one chunk per lane, their launches interleaved step by step: the transform kernels (one
+// LDS-filling workgroup per CU, their HBM traffic in phase-locked bursts) and the product kernel
+// (HBM streaming) of different chunks then share the chip instead of alternating on it (DESIGN.md
+// §4.5, §4.7).  The chunks are evened out over whole groups; a last group may have fewer lanes.
+// The library streams start after the caller's prior work and the allocation, and the caller's
+// stream resumes after them.  The three knobs are read per call.
+// A path passes what differs: make(lane) -> its kernel arguments for the lane, init(args, lane) ->
+// the launches before the first CMUX step, step(args, lane, i) -> those of step i (both return 0 or
+// an error code), and the accumulator order of the extract (rlog, gen_extract_kernel).
+// ------------------------------------------------------------------------------------------
+struct ChunkLane {
+  cplx* X;             // [chunk][K1 r][l q][T t][M] digit spectra
+  cplx* Y;             // [chunk][K1 c][L m][M] slot spectra
+  uint64_t* acc;       // [chunk][K1][N] accumulators
+  uint32_t base, cnt;  // first ciphertext of the chunk, ciphertexts in it
+  hipStream_t st;
+};
+
+template <class Make, class Init, class Step>
+static int run_chunks(const PbsArgs& a, const char* what, uint32_t L, uint32_t T, uint32_t rlog, Make&& make,
+                      Init&& init, Step&& step) {
+  constexpr int MAX_NS = 4;
+  const uint32_t K1 = a.k + 1, M = a.N / 2;
+  const uint64_t per_ct = generic_scratch_bytes_per_sample(a.k, a.N, a.level, a.base_log);
+  const uint64_t budget = env_knob("CONCRETE_HIP_GEN_BUDGET_MB", 2048) << 20;
+  const uint64_t cap = env_knob("CONCRETE_HIP_GEN_CHUNK", 65536);
+  const uint32_t chunk_max =
+      (uint32_t)std::min<uint64_t>(std::min<uint64_t>(a.num_samples, cap), std::max<uint64_t>(1, budget / per_ct));
+  uint32_t nchunks = (a.num_samples + chunk_max - 1) / chunk_max;
+  const int NS = (int)std::min<uint64_t>(std::min<uint64_t>(env_knob("CONCRETE_HIP_GEN_STREAMS", 2), MAX_NS), nchunks);
+  nchunks = (nchunks + NS - 1) / NS * NS;  // balanced groups of NS chunks
+  const uint32_t chunk = (a.num_samples + nchunks - 1) / nchunks;
+  hipStream_t st[MAX_NS];
+  for (int q = 0; q < NS; ++q) st[q] = q == 0 ? a.stream : side_stream(q);
+  void* scratch = nullptr;
+  keep_pool_memory();
+  CHIP_CHECK(hipMallocAsync(&scratch, per_ct * chunk * NS, a.stream));
+  hipEvent_t fork = nullptr;
+  if (NS > 1) {  // the library streams start after the caller's prior work and the allocation
+    CHIP_CHECK(hipEventCreateWithFlags(&fork, hipEventDisableTiming));
+    CHIP_CHECK(hipEventRecord(fork, a.stream));
+    for (int q = 1; q < NS; ++q) CHIP_CHECK(hipStreamWaitEvent(st[q], fork, 0));
+  }
+  using Args = decltype(make(std::declval<const ChunkLane&>()));
+  int rc = 0;
+  for (uint32_t base0 = 0; base0 < a.num_samples && rc == 0; base0 += NS * chunk) {
+    ChunkLane ln[MAX_NS];
+    Args ar[MAX_NS];
+    int nl = 0;  // lanes of this group: the last group's may end before NS
+    for (; nl < NS && base0 + nl * chunk < a.num_samples; ++nl) {
+      const uint32_t base = base0 + nl * chunk;
+      cplx* X = reinterpret_cast<cplx*>(static_cast<char*>(scratch) + (uint64_t)nl * per_ct * chunk);
+      cplx* Y = X + (uint64_t)chunk * K1 * a.level * T * M;
+      uint64_t* acc = reinterpret_cast<uint64_t*>(Y + (uint64_t)chunk * K1 * L * M);
+      ln[nl] = ChunkLane{X, Y, acc, base, std::min(chunk, a.num_samples - base), st[nl]};
+      ar[nl] = make(ln[nl]);
+    }
+    for (int q = 0; q < nl && rc == 0; ++q) rc = init(ar[q], ln[q]);
+    for (uint32_t i = 0; i < a.n && rc == 0; ++i)
+      for (int q = 0; q < nl && rc == 0; ++q) rc = step(ar[q], ln[q], i);
+    for (int q = 0; q < nl && rc == 0; ++q) {
+      const uint64_t total = ((uint64_t)a.k * a.N + 1) * ln[q].cnt;
+      const uint32_t eb = (uint32_t)std::min<uint64_t>((total + 255) / 256, 65535);
+      hipLaunchKernelGGL(gen_extract_kernel, dim3(eb), dim3(256), 0, st[q], a.out, a.out_idx, ln[q].acc, ln[q].base,
+                         ln[q].cnt, a.k, a.N, rlog);
+    }
+    if (rc == 0) rc = launch_ok(what);
+  }
+  for (int q = 1; q < NS; ++q) {  // the caller's stream resumes after the library streams' chunks
+    hipEvent_t join = nullptr;
+    CHIP_CHECK(hipEventCreateWithFlags(&join, hipEventDisableTiming));
+    CHIP_CHECK(hipEventRecord(join, st[q]));
+    CHIP_CHECK(hipStreamWaitEvent(a.stream, join, 0));
+    CHIP_CHECK(hipEventDestroy(join));
+  }
+  if (NS > 1) CHIP_CHECK(hipEventDestroy(fork));
+  CHIP_CHECK(hipFreeAsync(scratch, a.stream));
+  return rc;
+}
+
+// N >= 32768: the split path (S = N / 16384 workgroups per polynomial).
 // true: the register-tiled product ran, which leaves the slot spectra split by class (HPRE)
 template <int S>
 static bool launch_split_mac(const MacSplitArgs& m, uint32_t KL, uint32_t cnt, hipStream_t st) {
@@ -3005,114 +2972,51 @@ static bool launch_split_mac(const MacSplitArgs& m, uint32_t KL, uint32_t cnt, h
 template <int S>
 static void launch_split_front(const SplitArgs& s, uint32_t K1, hipStream_t st) {
   const dim3 grid(s.count * K1 * S);
-  if ((uint64_t)s.level * s.base_log <= 31)
+  if (narrow_state(s.level, s.base_log))
     hipLaunchKernelGGL((gen_split_front_kernel<S, true>), grid, dim3(512), 0, st, s);
   else
     hipLaunchKernelGGL((gen_split_front_kernel<S, false>), grid, dim3(512), 0, st, s);
 }
 
-// Chunks run in groups of NS on NS streams (the caller's and library streams, as the two-launch
-// path), their launches interleaved, so one chunk's product kernel (HBM streaming) runs beside
-// another's back / front kernels (one LDS-filling workgroup per CU).  CONCRETE_HIP_GEN_STREAMS=n
-// (1..4, default 2) sets NS.
+// The split path on the chunk driver: init, then per CMUX step the product, the back half and the
+// next step's front half.  CONCRETE_HIP_SPLIT_XCD=0: plain workgroup order (A/B).
 template <int S>
 static int pbs_split_launch(const PbsArgs& a, const KeyFormat& fmt, const Tables& tb, uint32_t T) {
   using G = Split<S>;
   const uint32_t K1 = a.k + 1, M = G::M, L = fmt.limbs;
-  const uint64_t per_ct = generic_scratch_bytes_per_sample(a.k, a.N, a.level, a.base_log);
-  const char* be = getenv("CONCRETE_HIP_GEN_BUDGET_MB");
-  const uint64_t budget = be && atoi(be) > 0 ? (uint64_t)atoi(be) << 20 : 2ull << 30;
-  const char* ce = getenv("CONCRETE_HIP_GEN_CHUNK");
-  const uint64_t cap = ce && atoi(ce) > 0 ? (uint64_t)atoi(ce) : 65536;
-  const uint32_t chunk_max = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(a.num_samples, cap),
-                                                          std::max<uint64_t>(1, budget / per_ct));
-  uint32_t nchunks = (a.num_samples + chunk_max - 1) / chunk_max;
-  constexpr int MAX_NS = 4;
-  const char* se = getenv("CONCRETE_HIP_GEN_STREAMS");
-  const int want = se && atoi(se) >= 1 ? std::min(atoi(se), MAX_NS) : 2;
-  const int NS = (int)std::min<uint32_t>((uint32_t)want, nchunks);
-  nchunks = (nchunks + NS - 1) / NS * NS;  // balanced groups of NS chunks
-  const uint32_t chunk = (a.num_samples + nchunks - 1) / nchunks;
-  hipStream_t st[MAX_NS];
-  for (int q = 0; q < MAX_NS; ++q) st[q] = q == 0 || q >= NS ? a.stream : side_stream(q);
-  void* scratch = nullptr;
-  keep_pool_memory();
-  CHIP_CHECK(hipMallocAsync(&scratch, per_ct * chunk * NS, a.stream));
-  hipEvent_t ev_in = nullptr;
-  if (NS > 1) {  // the library streams start after the caller's prior work and the allocation
-    CHIP_CHECK(hipEventCreateWithFlags(&ev_in, hipEventDisableTiming));
-    CHIP_CHECK(hipEventRecord(ev_in, a.stream));
-    for (int q = 1; q < NS; ++q) CHIP_CHECK(hipStreamWaitEvent(st[q], ev_in, 0));
-  }
-  const char* xe = getenv("CONCRETE_HIP_SPLIT_XCD");  // 0: plain workgroup order (A/B)
-  const bool xcd = !(xe && atoi(xe) == 0);
+  const char* xe = getenv("CONCRETE_HIP_SPLIT_XCD");
+  const uint32_t xcd = xe && atoi(xe) == 0 ? 0u : 1u;
   struct Lane {
     SplitArgs s;
     MacSplitArgs m;
-    uint32_t cnt;
   };
-  int rc = 0;
-  for (uint32_t base0 = 0; base0 < a.num_samples && rc == 0; base0 += NS * chunk) {
-    Lane ln[MAX_NS];
-    int nl = 0;
-    for (int q = 0; q < NS; ++q) {
-      const uint32_t base = base0 + q * chunk;
-      if (base >= a.num_samples) break;
-      const uint32_t cnt = std::min(chunk, a.num_samples - base);
-      cplx* X = reinterpret_cast<cplx*>(static_cast<char*>(scratch) + (uint64_t)q * per_ct * chunk);
-      cplx* Y = X + (uint64_t)chunk * K1 * a.level * T * M;
-      uint64_t* acc = reinterpret_cast<uint64_t*>(Y + (uint64_t)chunk * K1 * L * M);
-      ln[q].s = SplitArgs{acc, X, Y, tb.Tau, tb.WR, a.in, a.in_idx, a.luts, a.lut_idx, a.resid,
-                          base, cnt, a.n, a.k, a.level, a.base_log, fmt.bits, L, T, 0};
-      ln[q].s.xcd = xcd ? 1u : 0u;
-      ln[q].m = MacSplitArgs{X, Y, reinterpret_cast<const cplx*>(a.fbsk), tb.WR, cnt, a.k, a.level, L, T, M, G::R, 0};
-      ln[q].cnt = cnt;
-      ++nl;
-    }
-    for (int q = 0; q < nl; ++q) {
-      const uint64_t elems = (uint64_t)ln[q].cnt * K1 * a.N;
-      hipLaunchKernelGGL((gen_split_init_kernel<S>), dim3((uint32_t)std::min<uint64_t>((elems + 255) / 256, 65535)),
-                         dim3(256), 0, st[q], ln[q].s);
-      launch_split_front<S>(ln[q].s, K1, st[q]);
-    }
-    for (uint32_t i = 0; i < a.n; ++i) {
-      for (int q = 0; q < nl; ++q) {
-        Lane& l = ln[q];
+  return run_chunks(
+      a, "pbs (split)", L, T, (uint32_t)G::LOGR,
+      [&](const ChunkLane& c) {
+        const cplx* key = reinterpret_cast<const cplx*>(a.fbsk);
+        return Lane{SplitArgs{c.acc, c.X, c.Y, tb.Tau, tb.WR, a.in, a.in_idx, a.luts, a.lut_idx, a.resid, c.base, c.cnt,
+                              a.n, a.k, a.level, a.base_log, fmt.bits, L, T, 0, xcd},
+                    MacSplitArgs{c.X, c.Y, key, tb.WR, c.cnt, a.k, a.level, L, T, M, G::R, 0}};
+      },
+      [&](Lane& l, const ChunkLane& c) {
+        const uint64_t elems = (uint64_t)c.cnt * K1 * a.N;
+        hipLaunchKernelGGL((gen_split_init_kernel<S>), dim3((uint32_t)std::min<uint64_t>((elems + 255) / 256, 65535)),
+                           dim3(256), 0, c.st, l.s);
+        launch_split_front<S>(l.s, K1, c.st);
+        return 0;
+      },
+      [&](Lane& l, const ChunkLane& c, uint32_t i) {
         l.m.i = i;
-        if (launch_split_mac<S>(l.m, K1 * a.level, l.cnt, st[q]))
-          hipLaunchKernelGGL((gen_split_back_kernel<S, true>), dim3(l.cnt * K1 * S), dim3(512), 0, st[q], l.s);
+        if (launch_split_mac<S>(l.m, K1 * a.level, c.cnt, c.st))
+          hipLaunchKernelGGL((gen_split_back_kernel<S, true>), dim3(c.cnt * K1 * S), dim3(512), 0, c.st, l.s);
         else
-          hipLaunchKernelGGL((gen_split_back_kernel<S, false>), dim3(l.cnt * K1 * S), dim3(512), 0, st[q], l.s);
+          hipLaunchKernelGGL((gen_split_back_kernel<S, false>), dim3(c.cnt * K1 * S), dim3(512), 0, c.st, l.s);
         if (i + 1 < a.n) {
           l.s.step = i + 1;
-          launch_split_front<S>(l.s, K1, st[q]);
+          launch_split_front<S>(l.s, K1, c.st);
         }
-      }
-    }
-    for (int q = 0; q < nl; ++q) {
-      const uint64_t total = ((uint64_t)a.k * a.N + 1) * ln[q].cnt;
-      const uint32_t eb = (uint32_t)std::min<uint64_t>((total + 255) / 256, 65535);
-      hipLaunchKernelGGL(gen_extract_kernel, dim3(eb), dim3(256), 0, st[q], a.out, a.out_idx, ln[q].s.acc,
-                         ln[q].s.base, ln[q].cnt, a.k, a.N, (uint32_t)G::LOGR);
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-      set_error("generic pbs (split) launch failed: %s", hipGetErrorString(e));
-      rc = -1;
-    }
-  }
-  if (NS > 1) {  // the caller's stream resumes after the library streams' chunks
-    for (int q = 1; q < NS; ++q) {
-      hipEvent_t ev = nullptr;
-      CHIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-      CHIP_CHECK(hipEventRecord(ev, st[q]));
-      CHIP_CHECK(hipStreamWaitEvent(a.stream, ev, 0));
-      CHIP_CHECK(hipEventDestroy(ev));
-    }
-    CHIP_CHECK(hipEventDestroy(ev_in));
-  }
-  CHIP_CHECK(hipFreeAsync(scratch, a.stream));
-  return rc;
+        return 0;
+      });
 }
 
 template <int S>
@@ -3134,12 +3038,7 @@ static int convert_split_launch(const ConvertArgs& a, const KeyFormat& fmt, cons
                        dim3(256), 0, a.stream, c);
   }
   CHIP_CHECK(hipFreeAsync(scratch, a.stream));
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("generic convert (split) launch failed: %s", hipGetErrorString(e));
-    return -1;
-  }
-  return 0;
+  return launch_ok("convert (split)");
 }
 
 }  // namespace gen
@@ -3149,22 +3048,6 @@ uint64_t generic_scratch_bytes_per_sample(uint32_t k, uint32_t N, uint32_t level
   if (f.kind != KeyKind::GENERIC) return 0;
   const uint64_t K1 = k + 1, M = N / 2, T = (base_log + f.bits - 1) / f.bits;
   return K1 * level * T * M * 16 + K1 * f.limbs * M * 16 + K1 * N * 8;
-}
-
-// A second stream per device for the two-launch and split paths' chunk groups (created once, never
-// destroyed: it lives as long as the process, like the device tables).
-static hipStream_t side_stream(int idx) {
-  static std::mutex mu;
-  static std::map<std::pair<int, int>, hipStream_t> streams;
-  int dev = 0;
-  CHIP_CHECK(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> g(mu);
-  auto it = streams.find({dev, idx});
-  if (it != streams.end()) return it->second;
-  hipStream_t s = nullptr;
-  CHIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  streams[{dev, idx}] = s;
-  return s;
 }
 
 int pbs_generic_launch(const PbsArgs& a) {
@@ -3188,121 +3071,37 @@ int pbs_generic_launch(const PbsArgs& a) {
   {
     const FusedArgs f{a.out, a.out_idx, a.in, a.in_idx, a.luts, a.lut_idx, reinterpret_cast<const cplx*>(a.fbsk),
                       tb.Tau, a.resid, a.num_samples, a.n, a.base_log, b};
-    if (fused_dispatch(f, a.k, a.N, a.level, T, L, a.stream)) {
-      hipError_t e = hipGetLastError();
-      if (e != hipSuccess) {
-        set_error("generic pbs (fused) launch failed: %s", hipGetErrorString(e));
-        return -1;
-      }
-      return 0;
-    }
+    if (fused_dispatch(f, a.k, a.N, a.level, T, L, a.stream)) return launch_ok("pbs (fused)");
   }
   {
     const TileArgs t{a.out,   a.out_idx, a.in,    a.in_idx, a.luts,         a.lut_idx, reinterpret_cast<const cplx*>(a.fbsk),
                      tb.Wfull, tb.Z,     a.resid, a.num_samples, a.n, a.base_log, b};
-    if (tile_dispatch(a.N, K1, K1 * a.level, T, L, t, a.stream)) {
-      hipError_t e = hipGetLastError();
-      if (e != hipSuccess) {
-        set_error("generic pbs (tile) launch failed: %s", hipGetErrorString(e));
-        return -1;
-      }
-      return 0;
-    }
+    if (tile_dispatch(a.N, K1, K1 * a.level, T, L, t, a.stream)) return launch_ok("pbs (tile)");
   }
-  // Two-launch path: chunks of <= 2 GB of X / Y / accumulator scratch.  With two or more chunks,
-  // groups of NS chunks run on NS streams (the caller's and library streams of the device), their
-  // launches interleaved: the step kernel (one LDS-filling workgroup per CU, its HBM traffic in
-  // phase-locked bursts) and the product kernel (HBM streaming) of different chunks then share
-  // the chip instead of alternating on it.  CONCRETE_HIP_GEN_STREAMS=n (1..4, default 2) sets NS.
-  const uint64_t per_ct = generic_scratch_bytes_per_sample(a.k, a.N, a.level, a.base_log);
-  const char* be = getenv("CONCRETE_HIP_GEN_BUDGET_MB");  // scratch per chunk (A/B runs)
-  const uint64_t budget = be && atoi(be) > 0 ? (uint64_t)atoi(be) << 20 : 2ull << 30;
-  // CONCRETE_HIP_GEN_CHUNK caps the ciphertexts per chunk (tests: several chunks at small batches);
-  // both knobs are read per call
-  const char* ce = getenv("CONCRETE_HIP_GEN_CHUNK");
-  const uint64_t cap = ce && atoi(ce) > 0 ? (uint64_t)atoi(ce) : 65536;
-  const uint32_t chunk_max = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(a.num_samples, cap),
-                                                          std::max<uint64_t>(1, budget / per_ct));
-  uint32_t nchunks = (a.num_samples + chunk_max - 1) / chunk_max;
-  constexpr int MAX_NS = 4;
-  const char* se = getenv("CONCRETE_HIP_GEN_STREAMS");
-  const int want = se && atoi(se) >= 1 ? std::min(atoi(se), MAX_NS) : 2;
-  const int NS = (int)std::min<uint32_t>((uint32_t)want, nchunks);
-  nchunks = (nchunks + NS - 1) / NS * NS;  // balanced groups of NS chunks
-  const uint32_t chunk = (a.num_samples + nchunks - 1) / nchunks;
-  hipStream_t st[MAX_NS];
-  for (int q = 0; q < MAX_NS; ++q) st[q] = q == 0 || q >= NS ? a.stream : side_stream(q);
-  hipEvent_t ev_in = nullptr, ev_out[MAX_NS] = {};
-  void* scratch = nullptr;
-  keep_pool_memory();
-  CHIP_CHECK(hipMallocAsync(&scratch, per_ct * chunk * NS, a.stream));
-  if (NS > 1) {  // the library streams start after the caller's prior work and the allocation
-    CHIP_CHECK(hipEventCreateWithFlags(&ev_in, hipEventDisableTiming));
-    CHIP_CHECK(hipEventRecord(ev_in, a.stream));
-    for (int q = 1; q < NS; ++q) CHIP_CHECK(hipStreamWaitEvent(st[q], ev_in, 0));
-  }
+  // Two-launch path on the chunk driver: init and front, then per CMUX step the product and the step
+  // kernel (back half and the next step's front half)
   struct Lane {
     StepArgs s;
     MacArgs m;
-    uint64_t* acc;
-    uint32_t cnt;
   };
-  int rc = 0;
-  for (uint32_t base0 = 0; base0 < a.num_samples && rc == 0; base0 += NS * chunk) {
-    Lane ln[MAX_NS];
-    int nl = 0;
-    for (int q = 0; q < NS; ++q) {
-      const uint32_t base = base0 + q * chunk;
-      if (base >= a.num_samples) break;
-      const uint32_t cnt = std::min(chunk, a.num_samples - base);
-      cplx* X = reinterpret_cast<cplx*>(static_cast<char*>(scratch) + (uint64_t)q * per_ct * chunk);
-      cplx* Y = X + (uint64_t)chunk * K1 * a.level * T * M;
-      uint64_t* acc = reinterpret_cast<uint64_t*>(Y + (uint64_t)chunk * K1 * L * M);
-      ln[q].s = StepArgs{acc,     X,    Y,   tb.Wfull, tb.Wlo,  tb.Whi,     tb.Z, a.in, a.in_idx, a.luts, a.lut_idx,
-                         a.resid, base, cnt, a.n,      a.k,     a.level,    a.base_log, b, L,      T,      0, tb.Tau};
-      ln[q].m = MacArgs{X, Y, reinterpret_cast<const cplx*>(a.fbsk), cnt, a.k, a.level, L, T, M, 0};
-      ln[q].acc = acc;
-      ln[q].cnt = cnt;
-      ++nl;
-    }
-    for (int q = 0; q < nl && rc == 0; ++q) rc = step_dispatch<MODE_INIT | MODE_FRONT>(a.N, ln[q].s, K1, st[q]);
-    for (uint32_t i = 0; i < a.n && rc == 0; ++i) {
-      for (int q = 0; q < nl && rc == 0; ++q) {
-        Lane& l = ln[q];
+  return run_chunks(
+      a, "pbs", L, T, four_step(a.N) ? (uint32_t)__builtin_ctz(M / 512) : 0u,
+      [&](const ChunkLane& c) {
+        return Lane{StepArgs{c.acc, c.X, c.Y, tb.Wfull, tb.Wlo, tb.Whi, tb.Z, a.in, a.in_idx, a.luts, a.lut_idx,
+                             a.resid, c.base, c.cnt, a.n, a.k, a.level, a.base_log, b, L, T, 0, tb.Tau},
+                    MacArgs{c.X, c.Y, reinterpret_cast<const cplx*>(a.fbsk), c.cnt, a.k, a.level, L, T, M, 0}};
+      },
+      [&](Lane& l, const ChunkLane& c) { return step_dispatch<MODE_INIT | MODE_FRONT>(a.N, l.s, K1, c.st); },
+      [&](Lane& l, const ChunkLane& c, uint32_t i) {
         l.m.i = i;
-        if (!launch_mac2(l.m, l.cnt, st[q])) {
-          const dim3 mg((M + 255) / 256, K1 * L, (l.cnt + MAC_CTS - 1) / MAC_CTS);
-          hipLaunchKernelGGL(gen_mac_kernel, mg, dim3(256), 0, st[q], l.m);
+        if (!launch_mac2(l.m, c.cnt, c.st)) {
+          const dim3 mg((M + 255) / 256, K1 * L, (c.cnt + MAC_CTS - 1) / MAC_CTS);
+          hipLaunchKernelGGL(gen_mac_kernel, mg, dim3(256), 0, c.st, l.m);
         }
         l.s.step = i + 1;
-        rc = i + 1 < a.n ? step_dispatch<MODE_BACK | MODE_FRONT>(a.N, l.s, K1, st[q])
-                         : step_dispatch<MODE_BACK>(a.N, l.s, K1, st[q]);
-      }
-    }
-    for (int q = 0; q < nl && rc == 0; ++q) {
-      const uint64_t total = ((uint64_t)a.k * a.N + 1) * ln[q].cnt;
-      const uint32_t eb = (uint32_t)std::min<uint64_t>((total + 255) / 256, 65535);
-      const uint32_t rlog = four_step(a.N) ? (uint32_t)__builtin_ctz(M / 512) : 0u;
-      hipLaunchKernelGGL(gen_extract_kernel, dim3(eb), dim3(256), 0, st[q], a.out, a.out_idx, ln[q].acc, ln[q].s.base,
-                         ln[q].cnt, a.k, a.N, rlog);
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-      set_error("generic pbs launch failed: %s", hipGetErrorString(e));
-      rc = -1;
-    }
-  }
-  if (NS > 1) {  // the caller's stream resumes after the library streams' chunks
-    for (int q = 1; q < NS; ++q) {
-      CHIP_CHECK(hipEventCreateWithFlags(&ev_out[q], hipEventDisableTiming));
-      CHIP_CHECK(hipEventRecord(ev_out[q], st[q]));
-      CHIP_CHECK(hipStreamWaitEvent(a.stream, ev_out[q], 0));
-      CHIP_CHECK(hipEventDestroy(ev_out[q]));
-    }
-    CHIP_CHECK(hipEventDestroy(ev_in));
-  }
-  CHIP_CHECK(hipFreeAsync(scratch, a.stream));
-  return rc;
+        return i + 1 < a.n ? step_dispatch<MODE_BACK | MODE_FRONT>(a.N, l.s, K1, c.st)
+                           : step_dispatch<MODE_BACK>(a.N, l.s, K1, c.st);
+      });
 }
 
 int convert_bsk_generic_launch(const ConvertArgs& a) {
@@ -3333,12 +3132,7 @@ int convert_bsk_generic_launch(const ConvertArgs& a) {
     default: set_error("generic BSK conversion: N=%u", a.N); return -2;
   }
 #undef GEN_CONV
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("generic convert launch failed: %s", hipGetErrorString(e));
-    return -1;
-  }
-  return 0;
+  return launch_ok("convert");
 }
 
 }  // namespace chip

@@ -234,6 +234,44 @@ def test_generic_chunked_two_streams(B, oracle, torch_cuda, ci, streams, monkeyp
     assert np.array_equal(B.to_host(out), ref)
 
 
+@pytest.mark.parametrize("ci", [5, 13], ids=[CASES[i][0] for i in (5, 13)])
+def test_generic_chunked_ragged_group(B, oracle, torch_cuda, ci, monkeypatch):
+    """The chunk driver's ragged last group, on the two-launch path (N = 4096, one-launch kernel off)
+    and the split path (N = 2^15): CONCRETE_HIP_GEN_CHUNK=2 and CONCRETE_HIP_GEN_STREAMS=3 on 7
+    ciphertexts give chunks of 2 in groups of 3, so the second group has a single lane of one
+    ciphertext and its third lane's base lies past the batch.  Permuted input / output rows and mapped
+    LUTs: bit-exact vs the exact oracle and equal to the single-chunk run on the same inputs."""
+    label, k, N, n, l, logB, width = CASES[ci]
+    p, lwe_sk, glwe_sk, bsk, fbsk = setup(B, torch_cuda, k, N, n, l, logB, 7800)
+    rng = np.random.RandomState(17)
+    tables = [rng.randint(0, 1 << width, size=1 << width).astype(np.uint64) for _ in range(2)]
+    luts = np.stack([B.trivial_glwe(p, B.expand_lut(t, p.N, width)) for t in tables])
+    msgs = rng.randint(0, 1 << width, size=7)
+    cts = B.lwe_encrypt(lwe_sk, [B.encode(m, width) for m in msgs], p.n, 2.0 ** -30, 7803)
+    in_idx = np.array([4, 0, 6, 2, 5, 1, 3], dtype=np.uint64)
+    out_idx = np.array([2, 5, 0, 6, 1, 4, 3], dtype=np.uint64)
+    lut_idx = np.array([0, 1, 1, 0, 1, 0, 0], dtype=np.uint64)
+    dev = "cuda:0"
+    d = {name: B.to_device(a, dev) for name, a in (("in_idx", in_idx), ("out_idx", out_idx), ("lut_idx", lut_idx))}
+    monkeypatch.setenv("CONCRETE_HIP_GEN_FUSED", "0")  # N = 4096: the two-launch path, not gen_fused_kernel
+    monkeypatch.setenv("CONCRETE_HIP_GEN_STREAMS", "3")
+    outs = []
+    for chunk in ("2", None):
+        if chunk:
+            monkeypatch.setenv("CONCRETE_HIP_GEN_CHUNK", chunk)
+        else:
+            monkeypatch.delenv("CONCRETE_HIP_GEN_CHUNK")
+        out = torch_cuda.zeros((7, p.lwe_out_size), dtype=torch_cuda.int64, device=dev)
+        B.pbs(p, fbsk, B.to_device(cts, dev), B.to_device(luts, dev), out=out, **d)
+        torch_cuda.cuda.synchronize()
+        outs.append(B.to_host(out))
+    op = oracle.Params(n=p.n, k=p.k, N=p.N, l=p.level, logB=p.base_log)
+    ref, _ = oracle.pbs_batch(op, cts, luts, bsk=bsk, mode=oracle.MODE_KARATSUBA, lut_idx=lut_idx, in_idx=in_idx,
+                              out_idx=out_idx)
+    assert np.array_equal(outs[0], ref), f"{label}: ragged chunk groups differ from the exact oracle"
+    assert np.array_equal(outs[1], outs[0]), f"{label}: single chunk differs from the chunked run"
+
+
 @pytest.mark.parametrize("chunk", [None, "3"])
 @pytest.mark.parametrize("batch", [1, 2, 7])
 def test_generic_coop_kernel(B, oracle, torch_cuda, batch, chunk, monkeypatch):
