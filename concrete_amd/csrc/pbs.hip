@@ -505,8 +505,10 @@ pbs1024_pair_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
 //   forward:             levels 0 and 1 together — level 0 waits in registers during the second
 //                        transform, then v[0..7] -> own mailbox and level 1 -> own transpose
 //                        scratch (idle between transforms) | workgroup barrier | every wave reads
-//                        its slot from the 8 mailboxes and 8 scratches; level 2 through the
-//                        mailbox alone | workgroup barrier | reads
+//                        its slot from the 8 mailboxes and 8 scratches; the third transform, with
+//                        the first window's level-0/1 products (64 of its 96 FMAs) behind the
+//                        writes and reads of its LDS transpose (SLOT_L2_WINDOW); level 2 through
+//                        the mailbox alone | workgroup barrier | reads
 //   products, per limb:  Y[ct][co] -> mailbox of wave (ct, co) at position w | workgroup barrier |
 //                        the wave reads its 8 slots; limb li + 1's first product window; inverse
 //                        and recombination of limb li
@@ -532,6 +534,48 @@ pbs1024_pair_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
 #ifndef SLOT_DEFAULT
 #define SLOT_DEFAULT 1  // the planned call's pair part runs the slot-split kernel
 #endif
+// Schedule stages of DESIGN.md §4.16, one switch each (each A/B-tested alone and on top of the
+// kept ones).  Figures: slowest run over the parent's fastest on the same box
+// (profiles/r11_slot/variants.json, which also holds the sub-variants that were measured and
+// deleted); the kernel sits at 256 VGPRs, and a stage that moves the register allocation moves
+// the time by more than the work it saves or hides.
+#ifndef SLOT_INV_FOLD
+#define SLOT_INV_FOLD 1  // the inverse's last twiddle psi^m and the rounding as two FMAs per part: alone -1.1 %, on SLOT_L2_WINDOW a gain
+#endif
+#ifndef SLOT_FWD_IL
+#define SLOT_FWD_IL 0  // forward levels 0 and 1 as one interleaved pair of transforms: -0.7 %
+#endif
+#ifndef SLOT_L2_WINDOW
+#define SLOT_L2_WINDOW 1  // first window's level-0/1 products inside the third transform's transpose: +1.75 %
+#endif
+#ifndef SLOT_INV_SPLIT
+#define SLOT_INV_SPLIT 0  // early window split around the inverse's pass 1 and transpose writes: -3.2 %
+#endif
+// SLOT_LANE_AGAIN: with SLOT_L2_WINDOW the lane index, needed again only by the sample extract,
+// is the one value spilled across the step loop; taking it again from mbcnt removes the spill.
+// The plain build has no spill with SLOT_INV_FOLD and loses 0.8 % to the recompute, so 1 applies
+// it to the RESID build only; without the fold every build needs it (2).
+#ifndef SLOT_LANE_AGAIN
+#define SLOT_LANE_AGAIN (SLOT_L2_WINDOW && !SLOT_INV_FOLD ? 2 : 1)
+#endif
+static_assert(!SLOT_FWD_IL || SLOT_FWD_PAIR, "the interleaved pair is traded in one exchange");
+static_assert(!SLOT_L2_WINDOW || (SLOT_Y_EARLY && SLOT_QMAJOR && SLOT_FWD_PAIR),
+              "the first window's first four products must need levels 0 and 1 only");
+static_assert(!SLOT_INV_SPLIT || SLOT_Y_EARLY, "the split window is the early one");
+// tan(pi m / 16), m = 0..7 (correctly rounded): psi^m = psi_pow(m).re * (1 + i psi_tan(m))
+__device__ __forceinline__ double psi_tan(int m) {
+  constexpr double TAN[8] = {0.0,
+                             0x1.975f5e0553158p-3,
+                             0x1.a827999fcef32p-2,
+                             0x1.561b82ab7f990p-1,
+                             1.0,
+                             0x1.7f218e25a7461p+0,
+                             0x1.3504f333f9de6p+1,
+                             0x1.41bfee2424771p+2};
+  return TAN[m];
+}
+// the order of the stages' pieces as written, kept against the instruction scheduler
+__device__ __forceinline__ void slot_order() { __builtin_amdgcn_sched_barrier(0); }
 constexpr int SLOT_MBOX = 512;// complex values per mailbox: 8 slots x 64 lanes
 constexpr size_t pbs1024_pair_slot_lds_bytes() {
   return PBS1024_TABLE_BYTES + 2 * (size_t)PBS_PAIRS * (PBS1024_XCH_SLOTS + SLOT_MBOX) * 16 + 16;  // + the counter
@@ -674,28 +718,142 @@ pbs1024_pair_slot_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict_
     // ---- forward transforms of my polynomial, one level at a time; X[q][u]: slot w of the
     //      level-q spectrum of wave u (ciphertext u / 2, row u % 2)
     cplx X[L][NW];
-    cplx hold[8];  // SLOT_FWD_PAIR: the level-0 spectrum during the second transform
-    (void)hold;
+    const int hi = lane >> 3, lo = lane & 7;
+    // products e0 <= e < e1 of one window (output co of limb li for the 4 ciphertexts), in
+    // row-major (ro, q) order, or SLOT_QMAJOR: level-major (q, ro), which needs the last forward
+    // level's spectra only in the last third of a window.  Y is set by product 0 (no zeroing).
+    auto window_part = [&](cplx (&Y)[P], auto LIc, auto COc, auto E0c, auto E1c) __attribute__((always_inline)) {
+      constexpr int li = decltype(LIc)::value, co = decltype(COc)::value;
 #pragma unroll
-    for (int q = 0; q < L; ++q) {
-      cplx v[8];
+      for (int e = decltype(E0c)::value; e < decltype(E1c)::value; ++e) {
+        const int ro = SLOT_QMAJOR ? e % K1 : e / L, q = SLOT_QMAJOR ? e / K1 : e % L;
+        const int t = (li * K1 + co) * K1 * L + e;
+        const cplx gv = g[t % PF];
+#pragma unroll
+        for (int c = 0; c < P; ++c) {
+          const cplx x = X[q][2 * c + ro];
+          if (e == 0) {  // fma(a, b, 0) == a * b: same bits as accumulating from 0
+            Y[c].re = __builtin_fma(x.re, gv.re, -x.im * gv.im);
+            Y[c].im = __builtin_fma(x.re, gv.im, x.im * gv.re);
+          } else {
+            Y[c].re = __builtin_fma(x.re, gv.re, __builtin_fma(-x.im, gv.im, Y[c].re));
+            Y[c].im = __builtin_fma(x.re, gv.im, __builtin_fma(x.im, gv.re, Y[c].im));
+          }
+        }
+        // refill: the loads of a step are spread over its six product windows (§4.11)
+        g[t % PF] = t + PF < NKEY ? key_load(key_step, t + PF) : key_load(key_next, t + PF - NKEY);
+      }
+    };
+    // a finished window goes into the mailboxes of the waves (ct, co) at my position.  Before a
+    // limb's first window is sent, every wave must have read the previous exchange (the last
+    // forward level, or the previous limb's Y).
+    auto window_send = [&](cplx (&Y)[P], auto COc) __attribute__((always_inline)) {
+      constexpr int co = decltype(COc)::value;
+#pragma unroll
+      for (int c = 0; c < P; ++c) pin(Y[c]);
+      if (co == 0) spin_until_ge(ctr, NW * rcnt, guard);
+#pragma unroll
+      for (int c = 0; c < P; ++c) mbox_all[(2 * c + co) * MB + w * 64 + lane] = Y[c];
+    };
+    constexpr std::integral_constant<int, 0> I0{};
+    constexpr std::integral_constant<int, K1 * L> IE{};
+    // the first four products of a level-major window need levels 0 and 1 only, the first three
+    // are half of it
+    constexpr std::integral_constant<int, 2 * K1> IQ2{};
+    constexpr std::integral_constant<int, K1 * L / 2> IH{};
+    auto window = [&](auto LIc, auto COc) __attribute__((always_inline)) {
+      cplx Y[P];
+      window_part(Y, LIc, COc, I0, IE);
+      window_send(Y, COc);
+    };
+    auto digits = [&](cplx (&v)[8], int q) __attribute__((always_inline)) {
       int32_t d[16];
 #pragma unroll
       for (int m = 0; m < 16; ++m)
         d[m] = decomp_level32(st[m], (uint32_t)(q * logB), logB, half_m1, neg_base, q + 1 < L);
 #pragma unroll
       for (int m = 0; m < 8; ++m) v[m] = {(double)d[m], (double)d[m + 8]};
+    };
+    cplx Y0[P];  // SLOT_L2_WINDOW: window (limb 0, output 0), begun inside the third transform
+    (void)Y0;
+#if SLOT_FWD_IL
+    // Levels 0 and 1 as one interleaved pair: each transform's trip through the transpose scratch
+    // lies under the other's radix-8 pass.  One scratch serves both (a wave's LDS operations
+    // execute in issue order, and R2(0) is issued before W2(1)).
+    {
+      cplx v0[8], v1[8];
+      digits(v0, 0);
+      digits(v1, 1);
       cplx tw2[4];
-      fwd_p2_tw(tw2, T, lane >> 3);
+      fwd_p2_tw(tw2, T, hi);
+      if (FWD_TW2_EARLY) __builtin_amdgcn_sched_barrier(0);
+      fwd_p1(v0);
+      fwd_p1(v1);
+      xpose_hi(v0);
+      xpose_hi(v1);
+      geo8<false>(v0, tw2);
+      fwd_w2(v0, xch, hi, lo);
+      wave_lds_fence();
+      // W2(0) | P2(1) | R2(0) W2(1) | P3(0) | R2(1) | P3(1)
+      slot_order();
+      geo8<false>(v1, tw2);
+      slot_order();
+      fwd_r2(v0, xch, hi, lo);
+      wave_lds_fence();
+      fwd_w2(v1, xch, hi, lo);
+      wave_lds_fence();
+      slot_order();
+      geo8<false>(v0, tw3);
+      slot_order();
+      fwd_r2(v1, xch, hi, lo);
+      wave_lds_fence();
+      geo8<false>(v1, tw3);
+      // level 0 to my mailbox, level 1 to my transpose scratch (idle between transforms)
+#pragma unroll
+      for (int k = 0; k < 8; ++k) mybox[k * 64] = v0[k], xch[k * 64 + lane] = v1[k];
+      lap(1);
+      pair_barrier();
+      lap(5);
+#pragma unroll
+      for (int u = 0; u < NW; ++u) X[0][u] = slotbox[u * MB], X[1][u] = xch_all[u * XS + w * 64 + lane];
+      slot_signal(ctr, lane, rcnt);
+    }
+#endif
+    cplx hold[8];  // SLOT_FWD_PAIR: the level-0 spectrum during the second transform
+    (void)hold;
+#pragma unroll
+    for (int q = SLOT_FWD_IL ? 2 : 0; q < L; ++q) {
+      cplx v[8];
+      digits(v, q);
+      cplx tw2[4];
+      fwd_p2_tw(tw2, T, hi);
       if (FWD_TW2_EARLY) __builtin_amdgcn_sched_barrier(0);
 #if SLOT_FWD_PAIR
       // Levels 0 and 1 are traded in one exchange: level 0 waits in registers during the second
       // transform, then goes to my mailbox and level 1 to my transpose scratch (idle between
       // transforms).  The third transform overwrites that scratch, so it first waits (right
       // before its first LDS write) until every wave has read the pair.
-      fft512_fwd_tw(v, xch, lane, tw2, tw3, 0ull, [&]() __attribute__((always_inline)) {
-        if (q == 2) spin_until_ge(ctr, NW * rcnt, guard);
-      });
+      if (SLOT_L2_WINDOW && q == 2) {
+        // the third transform with the first window's level-0/1 products behind its transpose's
+        // writes and reads (the reads queue behind the writes: LDS operations of a wave execute
+        // in issue order)
+        fwd_p1(v);
+        xpose_hi(v);
+        geo8<false>(v, tw2);
+        spin_until_ge(ctr, NW * rcnt, guard);
+        fwd_w2(v, xch, hi, lo);
+        wave_lds_fence();
+        fwd_r2(v, xch, hi, lo);
+        wave_lds_fence();
+        slot_order();
+        window_part(Y0, I0, I0, I0, IQ2);
+        slot_order();
+        geo8<false>(v, tw3);
+      } else {
+        fft512_fwd_tw(v, xch, lane, tw2, tw3, 0ull, [&]() __attribute__((always_inline)) {
+          if (q == 2) spin_until_ge(ctr, NW * rcnt, guard);
+        });
+      }
       if (q == 0) {
 #pragma unroll
         for (int k = 0; k < 8; ++k) hold[k] = v[k];
@@ -733,14 +891,40 @@ pbs1024_pair_slot_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict_
 
     // ---- per limb: products of my slot for the 4 ciphertexts and both outputs (key from
     //      registers, refilled PF values ahead), Y exchange, inverse of my polynomial.
+    // SLOT_INV_FOLD: v is the inverse's pass-3 output without its last twiddle conj(psi^m),
+    // psi^m = c (1 + i t): v conj(psi^m) = c (u + i u'), u = re + t im, u' = im - t re, and the
+    // product c u is rounded once, into the integer (RND_MAGIC - c u as one FMA).
     auto recombine = [&](const cplx (&v)[8], auto LIc) __attribute__((always_inline)) {
       constexpr int lr = decltype(LIc)::value;
+      // an FMA takes one scalar constant: the rounding constant goes through a vector register
+      // pair, set here instead of held for the whole step loop
+      double rnd = RND_MAGIC;
+      if (SLOT_INV_FOLD) pin(rnd);
 #pragma unroll
       for (int m = 0; m < 8; ++m) {
-        const double tr = RND_MAGIC - v[m].re, ti = RND_MAGIC - v[m].im;
-        if constexpr (RESID) {
-          max_resid = fmax(max_resid, fabs(v[m].re - (RND_MAGIC - tr)));
-          max_resid = fmax(max_resid, fabs(v[m].im - (RND_MAGIC - ti)));
+        double tr, ti;
+        if (SLOT_INV_FOLD && m > 0) {
+          // m > 4: psi^m = s (cot + i) with s = cos(pi (8 - m) / 16) and cot = tan(pi (8 - m) / 16),
+          // the constants of 8 - m (no tangent above 1, 7 scalar constants in all: 13 spill SGPRs)
+          const bool cot = m > 4;
+          const double c = psi_pow(cot ? 8 - m : m).re, t = psi_tan(cot ? 8 - m : m);
+          const double ur = cot ? __builtin_fma(t, v[m].re, v[m].im) : __builtin_fma(t, v[m].im, v[m].re);
+          const double ui = cot ? __builtin_fma(t, v[m].im, -v[m].re) : __builtin_fma(-t, v[m].re, v[m].im);
+          if constexpr (RESID) {  // the residual is taken on the value that is rounded
+            double pr = c * ur, pi = c * ui;
+            pin(pr), pin(pi);
+            tr = RND_MAGIC - pr, ti = RND_MAGIC - pi;
+            max_resid = fmax(max_resid, fabs(pr - (RND_MAGIC - tr)));
+            max_resid = fmax(max_resid, fabs(pi - (RND_MAGIC - ti)));
+          } else {
+            tr = __builtin_fma(-c, ur, rnd), ti = __builtin_fma(-c, ui, rnd);
+          }
+        } else {
+          tr = RND_MAGIC - v[m].re, ti = RND_MAGIC - v[m].im;
+          if constexpr (RESID) {
+            max_resid = fmax(max_resid, fabs(v[m].re - (RND_MAGIC - tr)));
+            max_resid = fmax(max_resid, fabs(v[m].im - (RND_MAGIC - ti)));
+          }
         }
         if constexpr (lr == 0) {
           B[m] += (uint64_t)__double_as_longlong(tr) - MAGIC_ALL_3;
@@ -751,47 +935,23 @@ pbs1024_pair_slot_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict_
         }
       }
     };
-    // one product window: output co of limb li for the 4 ciphertexts, then into the mailboxes of
-    // the waves (ct, co) at my position.  Before a limb's first window is sent, every wave must
-    // have read the previous exchange (the last forward level, or the previous limb's Y).
-    auto window = [&](auto LIc, auto COc) __attribute__((always_inline)) {
-      constexpr int li = decltype(LIc)::value, co = decltype(COc)::value;
-      cplx Y[P];  // set by the first product (no zeroing)
-#pragma unroll
-      for (int e = 0; e < K1 * L; ++e) {
-        // row-major (ro, q), or SLOT_QMAJOR: level-major (q, ro), which needs the last forward
-        // level's spectra only in the last third of a window
-        const int ro = SLOT_QMAJOR ? e % K1 : e / L, q = SLOT_QMAJOR ? e / K1 : e % L;
-        const int t = (li * K1 + co) * K1 * L + e;
-        const cplx gv = g[t % PF];
-#pragma unroll
-        for (int c = 0; c < P; ++c) {
-          const cplx x = X[q][2 * c + ro];
-          if (e == 0) {  // fma(a, b, 0) == a * b: same bits as accumulating from 0
-            Y[c].re = __builtin_fma(x.re, gv.re, -x.im * gv.im);
-            Y[c].im = __builtin_fma(x.re, gv.im, x.im * gv.re);
-          } else {
-            Y[c].re = __builtin_fma(x.re, gv.re, __builtin_fma(-x.im, gv.im, Y[c].re));
-            Y[c].im = __builtin_fma(x.re, gv.im, __builtin_fma(x.im, gv.re, Y[c].im));
-          }
-        }
-        // refill: the loads of a step are spread over its six product windows (§4.11)
-        g[t % PF] = t + PF < NKEY ? key_load(key_step, t + PF) : key_load(key_next, t + PF - NKEY);
-      }
-#pragma unroll
-      for (int c = 0; c < P; ++c) pin(Y[c]);
-      if (co == 0) spin_until_ge(ctr, NW * rcnt, guard);
-#pragma unroll
-      for (int c = 0; c < P; ++c) mbox_all[(2 * c + co) * MB + w * 64 + lane] = Y[c];
-    };
     // SLOT_Y_EARLY: the first window of limb li + 1 runs between the reads of limb li's Y and its
     // inverse, so the reads' latency (and the other waves' reads, which that window's mailbox
     // writes wait for) is covered by 96 FMAs instead of being exposed right behind the barrier.
-    if (SLOT_Y_EARLY) window(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
+    // SLOT_INV_SPLIT: that window is split around the inverse's pass 1 and transpose writes, so
+    // its second half covers the transpose's trip through LDS as well.
+    if (SLOT_L2_WINDOW) {
+      window_part(Y0, I0, I0, IQ2, IE);  // the level-2 products cover the rest of the X[2] reads
+      window_send(Y0, I0);
+    } else if (SLOT_Y_EARLY) {
+      window(I0, I0);
+    }
     static_for<0, LIMBS>([&](auto LI) __attribute__((always_inline)) {
       constexpr int li = decltype(LI)::value;
-      if (!SLOT_Y_EARLY) window(LI, std::integral_constant<int, 0>{});
-      window(LI, std::integral_constant<int, 1>{});
+      constexpr std::integral_constant<int, 1> I1{};
+      constexpr std::integral_constant<int, li + 1> LN{};
+      if (!SLOT_Y_EARLY) window(LI, I0);
+      window(LI, I1);
       lap(2);
       pair_barrier();
       lap(5);
@@ -800,13 +960,46 @@ pbs1024_pair_slot_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict_
       for (int k = 0; k < 8; ++k) vp[k] = mybox[k * 64];
       slot_signal(ctr, lane, rcnt);
       lap(3);
-      if constexpr (SLOT_Y_EARLY && li + 1 < LIMBS) {
-        window(std::integral_constant<int, li + 1>{}, std::integral_constant<int, 0>{});
-        lap(2);
-      }
       cplx gi2[4];  // inverse pass-2 stage twiddles, read ahead of the transpose
-      inv_p2_stage_tw(gi2, T, lane & 7);
-      fft512_inv_tw(vp, xch, T, lane, gi2, 0ull);
+      if constexpr (SLOT_INV_SPLIT && li + 1 < LIMBS) {
+        cplx Yn[P];
+        window_part(Yn, LN, I0, I0, IH);
+        slot_order();
+        inv_p1(vp, 0ull);
+        inv_w1(vp, xch, hi, lo);
+        wave_lds_fence();
+        slot_order();
+        window_part(Yn, LN, I0, IH, IE);
+        window_send(Yn, I0);
+        lap(2);
+        slot_order();
+        inv_p2_stage_tw(gi2, T, lo);
+        inv_r1(vp, xch, hi, lo);
+        wave_lds_fence();
+      } else {
+        if constexpr (SLOT_Y_EARLY && li + 1 < LIMBS) {
+          window(LN, I0);
+          lap(2);
+        }
+        inv_p2_stage_tw(gi2, T, lo);
+        inv_p1(vp, 0ull);
+        inv_w1(vp, xch, hi, lo);
+        wave_lds_fence();
+        inv_r1(vp, xch, hi, lo);
+        wave_lds_fence();
+      }
+      {  // the rest of the inverse (fft512_inv_tw): pass 2, its output twiddles (read after the
+         // transpose: their latency hides behind the butterflies), hi transpose, pass 3
+        cplx t1[8];
+#pragma unroll
+        for (int t = 0; t < 8; ++t) t1[t] = T.T1[hi * T1_STRIDE + 8 * t + lo];
+        geo8<true, true>(vp, gi2);
+#pragma unroll
+        for (int t = 0; t < 8; ++t) vp[t] = cmulc(vp[t], t1[t]);
+        xpose_hi(vp);
+        if (SLOT_INV_FOLD) dft8<true>(vp);  // conj(psi^m) is applied by recombine
+        else inv_p3(vp);
+      }
       recombine(vp, LI);
       // materialise B here (else the inverse tail sinks into the next limb's products)
 #pragma unroll
@@ -824,7 +1017,11 @@ pbs1024_pair_slot_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict_
     }
   }
 
-  // ---- sample extract (nth = 0) of acc = -B (pbs1024_pair_kernel)
+  // ---- sample extract (nth = 0) of acc = -B (pbs1024_pair_kernel).  SLOT_LANE_AGAIN: the lane index
+  //      is taken again (mbcnt of a full mask) instead of holding a register across the step loop.
+  const int lane_x = SLOT_LANE_AGAIN == 2 || (SLOT_LANE_AGAIN == 1 && RESID)
+                         ? (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u))
+                         : lane;
   uint64_t* o = out + (active ? (out_idx ? out_idx[s] : s) : 0) * (uint64_t)(K * N + 1);
   if (!active) {
   } else if (h == 0) {
@@ -833,15 +1030,15 @@ pbs1024_pair_slot_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict_
     wave_lds_fence();
 #pragma unroll
     for (int m = 0; m < 16; ++m) {
-      const int j = lane + 64 * m;
+      const int j = lane_x + 64 * m;
       const uint64_t v = xch64[(N - j) & (N - 1)];
       o[j] = j == 0 ? 0ull - v : v;
     }
-  } else if (lane == 0) {
+  } else if (lane_x == 0) {
     o[K * N] = 0ull - B[0];
   }
 
-  if constexpr (RESID && !STAMPS) report_resid(max_resid, lane, active, resid_out);
+  if constexpr (RESID && !STAMPS) report_resid(max_resid, lane_x, active, resid_out);
 }
 
 // ------------------------------------------------------------------------------------
