@@ -21,6 +21,15 @@
 #include "keycheck.hpp"
 #include "pbs.hpp"
 
+// No FMA contraction in this file.  The double-double routines below are error-free transformations:
+// they need p = rn(x y) and s = rn(p + e) as written.  Device code is compiled with -ffp-contract=fast,
+// and the AMDGPU backend fuses a product into its uses even when it has several (quick_two_sum(p, e)
+// became fma(x, y, e) and e - (fma(-x, y, s)), counting the product's rounding error twice): the stored
+// spectra were then off by ~2^-56 of the block's largest value instead of correctly rounded
+// (tests/test_gpu_key_accuracy.py).  The one fused operation that is meant is
+// written as __builtin_fma.
+#pragma clang fp contract(off)
+
 namespace chip {
 
 void keep_pool_memory();  // abi.hip: the default pool never releases (see there)
