@@ -1,7 +1,8 @@
 // kernel_util.hpp — device scaffolding shared by every fused PBS kernel (pbs.hip, pbs1024_quad.hip,
 // pbs1024_hex.hip, pbs2048.hip, pbs1024k2.hip, pbs_small.hip, pbs512k4.hip) and by pbs_generic.hip /
 // keyswitch.hip: the wave-group sync on LDS counters and its bounded spin, the LDS-DMA issue of a
-// key-ring group, the limb rounding constants and the RESID epilogue.
+// key-ring group, the limb rounding constants, the RESID epilogue and the step pieces
+// of the N = 1024, k = 1 family.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -185,4 +186,81 @@ __device__ __forceinline__ void wait_vmcnt() {
   __builtin_amdgcn_s_waitcnt((N_WAIT & 15) | (7 << 4) | (15 << 8) | ((N_WAIT >> 4) << 14));
 }
 
+// ------------------------------------------------------------------------------------
+// N = 1024, k = 1 family (pbs1024_pair_kernel, pbs1024_pair_slot_kernel, pbs1024_quad_kernel,
+// pbs1024_hex_kernel): the step pieces the four kernels share.  A polynomial's 1024 coefficients lie
+// 16 per lane, lane t holding t + 64 m; the kernels keep the NEGATED accumulator B = -acc.
+// ------------------------------------------------------------------------------------
+constexpr int N1K = 1024;
+
+// Coefficient lane + 64 m of B = -(LUT_poly * X^{-bt}), bt = ms(b) (blind_rotate_assign:
+// polynomial_wrapping_monic_monomial_div); 0 for a missing ciphertext.
+__device__ __forceinline__ uint64_t neg_acc_coeff(const uint64_t* lut, int poly, int lane, int m, uint32_t bt,
+                                                  bool active) {
+  const uint32_t src = (uint32_t)(lane + 64 * m + bt) & (2 * N1K - 1);
+  const uint64_t v = active ? lut[poly * N1K + (src & (N1K - 1))] : 0ull;
+  return src < N1K ? 0ull - v : v;
+}
+
+// ---- ct1 = acc * X^{at} - acc = B - X^{at} B, decomposer state per coefficient.
+//      Coefficient j = lane + 64 m reads B[src & (N-1)], src = j - at mod 2N, negated when
+//      src >= N; o = 8 src + 8N (mod 2^32) carries the byte offset in bits 0..12 and "src < N" in
+//      bit 13, so ct1 = B + (rv ^ s) - s with s = -(bit 13 of o).
+//      decomp_init(x) = (x >> nrep) + bit(nrep - 1) = (x + 2^(nrep-1)) >> nrep (a wrap of
+//      x + 2^(nrep-1) past 2^64 gives state 0 instead of 2^(l logB), both decomposing to zero
+//      digits); nrep >= 37 under the exactness gate, so only the high word is shifted: khi is
+//      2^(nrep-1) in the high word.
+__device__ __forceinline__ uint32_t rot_o0(int lane, uint32_t at) {
+  return ((uint32_t)(lane - (int)at) << 3) + 8u * N1K;
+}
+// the rotated coefficient of slot m, from the polynomial at `base` (LDS)
+__device__ __forceinline__ uint64_t rot_read(const uint64_t* base, uint32_t o0, int m) {
+  return *reinterpret_cast<const uint64_t*>(reinterpret_cast<const char*>(base) + ((o0 + 512u * m) & 8191u));
+}
+// the rotated term of slot m: -X^{at} B at coefficient lane + 64 m, from the value rv read there.
+// The kernel adds its B to it (rot_term + B: a helper that took B too fixed the order of the two
+// additions, and the slot kernel's listing moved with it).
+__device__ __forceinline__ uint64_t rot_term(uint64_t rv, uint32_t o0, int m) {
+  const uint32_t o = o0 + 512u * m;
+  const uint32_t s32 = (uint32_t)((int32_t)(o << 18) >> 31);
+  const uint64_t rvs = rv ^ (((uint64_t)s32 << 32) | s32);
+  return rvs + (uint64_t)(s32 & 1u);
+}
+// decomposer state of x = B + rot_term, a coefficient of ct1; khi = 1u << (nrep - 33)
+__device__ __forceinline__ uint32_t rot_state(uint64_t x, uint32_t khi, int nrep) {
+  return ((uint32_t)(x >> 32) + khi) >> (nrep - 32);
+}
+// B of a wave that holds it in registers, into its scratch xch64 (the rotation's first step)
+__device__ __forceinline__ void acc_to_scratch(uint64_t* xch64, int lane, const uint64_t (&B)[16]) {
+  lane &= 63;  // the lane's range, visible to the optimiser inside the helper as it is in the kernels
+#pragma unroll
+  for (int m = 0; m < 16; ++m) xch64[lane + 64 * m] = B[m];
+  wave_lds_fence();
+}
+// Recombination of limb LR.  bits(MAGIC - v) = MAGIC_BITS - round(v): the limb's exact integers,
+// negated (B = -acc), shifted into the accumulator.  The constant of all limbs is removed with limb 0
+// (it must not survive into the next step's rotation: X^a * const != const).
+static_assert(MAGIC_ALL_3 == RND_MAGIC_BITS + (RND_MAGIC_BITS << 22) + (RND_MAGIC_BITS << 43),
+              "three limbs at shifts 0, 22, 43");
+// tr, ti: the rounded parts RND_MAGIC - x
+template <int LR>
+__device__ __forceinline__ void limb_add(uint64_t& are, uint64_t& aim, double tr, double ti) {
+  if constexpr (LR == 0) {
+    are += (uint64_t)__double_as_longlong(tr) - MAGIC_ALL_3;
+    aim += (uint64_t)__double_as_longlong(ti) - MAGIC_ALL_3;
+  } else {
+    are += (uint64_t)__double_as_longlong(tr) << limb_shift(LR);
+    aim += (uint64_t)__double_as_longlong(ti) << limb_shift(LR);
+  }
+}
+// one complex value v of the inverse's output into the accumulators of its two coefficients
+template <int LR, bool RESID>
+__device__ __forceinline__ void recombine_one(uint64_t& are, uint64_t& aim, const cplx& v, double& max_resid) {
+  const double tr = RND_MAGIC - v.re, ti = RND_MAGIC - v.im;
+  if constexpr (RESID) {
+    max_resid = fmax(max_resid, fabs(v.re - (RND_MAGIC - tr)));
+    max_resid = fmax(max_resid, fabs(v.im - (RND_MAGIC - ti)));
+  }
+  limb_add<LR>(are, aim, tr, ti);
+}
 }  // namespace chip

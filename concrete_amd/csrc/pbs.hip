@@ -42,29 +42,13 @@
 
 namespace chip {
 
-static_assert(MAGIC_ALL_3 == RND_MAGIC_BITS + (RND_MAGIC_BITS << 22) + (RND_MAGIC_BITS << 43),
-              "three limbs at shifts 0, 22, 43");
-
-#ifndef FWD_LAST_VIA_WINDOW
-#define FWD_LAST_VIA_WINDOW 1  // last forward exchange published by the first key window's barrier
-#endif
-#ifndef FWD_TW2_EARLY
-#define FWD_TW2_EARLY 1  // forward pass-2 twiddles issued ahead of pass 1 (+0.4 %)
-#endif
 #ifndef DIAG_NOMAC
 #define DIAG_NOMAC 0  // diagnostic builds only: skip the key MAC (wrong results)
 #endif
 
-#ifndef FWD_XBATCH
-#define FWD_XBATCH 2  // forward levels traded per exchange (mailbox: 4 KB per level, <= 2)
-#endif
-#ifndef PAIR_FLAGS
-#define PAIR_FLAGS 1  // half-spectrum exchanges synchronise the two waves of a pair only
-#endif
-
 // Sync group (kernel_util.hpp group_*<2>): the two waves of a pair, f = the pair's counters, h = my
-// polynomial.  DIAG_NOXBAR: timing-only builds without any exchange synchronisation; PAIR_FLAGS = 0:
-// the half-spectrum exchanges hold up the whole workgroup instead.
+// polynomial: the half-spectrum exchanges synchronise the two waves of a pair only.  DIAG_NOXBAR:
+// timing-only builds without any exchange synchronisation.
 #if defined(DIAG_NOXBAR)
 constexpr bool XBAR = false;
 #else
@@ -78,8 +62,7 @@ __device__ __forceinline__ void pair_wait(uint32_t* f, int h, uint32_t cnt, cons
 }
 __device__ __forceinline__ void xchg_barrier(uint32_t* f, int h, uint32_t& cnt, const SyncGuard& guard) {
   if constexpr (!XBAR) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  else if constexpr (PAIR_FLAGS) group_sync<2>(f, h, cnt, guard);
-  else pair_barrier();
+  else group_sync<2>(f, h, cnt, guard);
 }
 
 template <int P, int L, bool RESID, bool STAMPS>
@@ -154,11 +137,7 @@ pbs1024_pair_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
   {
     const uint32_t bt = active ? modswitch(lwe[n], LOG2_2N) : 0u;
 #pragma unroll
-    for (int m = 0; m < 16; ++m) {
-      const uint32_t src = (uint32_t)(lane + 64 * m + bt) & (2 * N - 1);
-      const uint64_t v = active ? lut[h * N + (src & (N - 1))] : 0ull;
-      B[m] = src < N ? 0ull - v : v;
-    }
+    for (int m = 0; m < 16; ++m) B[m] = neg_acc_coeff(lut, h, lane, m, bt, active);
   }
 
   const int nrep = 64 - L * (int)base_log;
@@ -166,8 +145,17 @@ pbs1024_pair_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
   const int32_t neg_base = -(1 << logB);
   const uint32_t half_m1 = (1u << (logB - 1)) - 1u;
   double max_resid = 0.0;
+  // diagnostic stamps (STAMPS builds only): 0 rotation, 1 forward + exchange, 2 products, 8 key
+  // landed (vmcnt), 5 barrier wait, 3 Y exchange, 4 inverse + recombination, 6 total, 7 work steps
   uint64_t acc_t[NSTAMP] = {};
   uint64_t t_begin = 0, tp = 0;
+  auto lap = [&](int k) __attribute__((always_inline)) {
+    if constexpr (STAMPS) {
+      const uint64_t t = stamp();
+      acc_t[k] += t - tp;
+      tp = t;
+    }
+  };
   if constexpr (STAMPS) t_begin = stamp();
 
   // forward pass-3 twiddles of my lane: constant for the whole kernel, kept in registers
@@ -191,51 +179,32 @@ pbs1024_pair_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
       acc_t[7] += ai != 0ull && at != 0u;
     }
 
-    // ---- own polynomial: ct1 = acc * X^{at} - acc = B - X^{at} B, decomposer state per
-    //      coefficient.  Coefficient j = lane + 64 m reads B[src & (N-1)], src = j - at mod 2N,
-    //      negated when src >= N; o = 8 src + 8N (mod 2^32) carries the byte offset in bits 0..12
-    //      and "src < N" in bit 13, so ct1 = B + (rv ^ s) - s with s = -(bit 13 of o).
-    //      decomp_init(x) = (x >> nrep) + bit(nrep - 1) = (x + 2^(nrep-1)) >> nrep (a wrap of
-    //      x + 2^(nrep-1) past 2^64 gives state 0 instead of 2^(l logB), both decomposing to zero
-    //      digits); nrep >= 37 under the exactness gate, so only the high word is shifted.
+    // ---- own polynomial: ct1 = B - X^{at} B and the decomposer state per coefficient (the pieces and
+    //      their explanation: kernel_util.hpp)
     uint32_t st[16];
     {
-#pragma unroll
-      for (int m = 0; m < 16; ++m) xch64[lane + 64 * m] = B[m];
-      wave_lds_fence();
-      const uint32_t o0 = ((uint32_t)(lane - (int)at) << 3) + 8u * N;
-      const uint32_t khi = 1u << (nrep - 33);  // 2^(nrep-1) in the high word
+      acc_to_scratch(xch64, lane, B);
+      const uint32_t o0 = rot_o0(lane, at), khi = 1u << (nrep - 33);
       // all 16 reads in flight at once (left to itself the scheduler issues them four at a time,
       // one LDS round trip each)
       uint64_t rv[16];
 #pragma unroll
-      for (int m = 0; m < 16; ++m)
-        rv[m] = *reinterpret_cast<const uint64_t*>(reinterpret_cast<const char*>(xch64) + ((o0 + 512u * m) & 8191u));
+      for (int m = 0; m < 16; ++m) rv[m] = rot_read(xch64, o0, m);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int m = 0; m < 16; ++m) {
-        const uint32_t o = o0 + 512u * m;
-        const uint32_t s32 = (uint32_t)((int32_t)(o << 18) >> 31);
-        const uint64_t rvs = rv[m] ^ (((uint64_t)s32 << 32) | s32);
-        const uint64_t x = B[m] + rvs + (uint64_t)(s32 & 1u);
-        st[m] = ((uint32_t)(x >> 32) + khi) >> (nrep - 32);
-      }
+      for (int m = 0; m < 16; ++m) st[m] = rot_state(rot_term(rv[m], o0, m) + B[m], khi, nrep);
       wave_lds_fence();
     }
-    if constexpr (STAMPS) {
-      uint64_t t = stamp();
-      acc_t[0] += t - tp;
-      tp = t;
-    }
+    lap(0);
 
     // ---- forward transforms; keep my half of the slots, mail the other half -------------
     // Xo[q][j] / Xp[q][j]: spectrum of my own / my partner's digit polynomial (level q) at
     // frequency slot 4h + j.  The wave owning the upper half (h = 1) emits its spectrum in slot
     // order k2 ^ 4, so every wave keeps v[0..3] and mails v[4..7]: no h-dependent registers.
     cplx Xo[L][4], Xp[L][4];
-    // levels are traded in batches of up to FWD_XBATCH (one mailbox of 4 KB per level): the
+    // levels are traded in batches of up to XB (one mailbox of 4 KB per level, <= 2): the
     // mailed halves of a batch wait in registers until its last transform is done
-    constexpr int XB = FWD_XBATCH;
+    constexpr int XB = 2;
 #pragma unroll
     for (int q0 = 0; q0 < L; q0 += XB) {
       const int nq = (q0 + XB <= L) ? XB : L - q0;
@@ -259,7 +228,7 @@ pbs1024_pair_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
             // issued here, ahead of pass 1 and the register transpose that hide their latency
             // (left alone the scheduler sinks each read to its butterfly stage, one exposed LDS
             // round trip per stage)
-            if (FWD_TW2_EARLY) __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_sched_barrier(0);
             fft512_fwd_tw(v, xch, lane, tw2, tw3, hsign, [&]() __attribute__((always_inline)) {
               if (q0 > 0 && t == 0) pair_wait(pf, h, pcnt, guard);
             });
@@ -280,7 +249,7 @@ pbs1024_pair_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
       // (which drains every wave's LDS writes) publishes them, and they are first used in the
       // second window (row 1); they are read right after that barrier.
       const bool last_batch = q0 + XB >= L;
-      if (!last_batch || !FWD_LAST_VIA_WINDOW) {
+      if (!last_batch) {
         xchg_barrier(pf, h, pcnt, guard);
 #pragma unroll
         for (int t = 0; t < XB; ++t)
@@ -299,35 +268,10 @@ pbs1024_pair_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
       // workgroup barriers.
       if (q0 + XB < L) pair_signal(pf, h, pcnt);
     }
-    if constexpr (STAMPS) {
-      uint64_t t = stamp();
-      acc_t[1] += t - tp;
-      tp = t;
-    }
+    lap(1);
 
     // ---- per limb: MAC for both output polynomials on my half (key from the LDS ring),
     //      trade halves through the mailbox, inverse transform of my polynomial. ------------
-    // bits(MAGIC - v) = MAGIC_BITS - round(v): limb li's exact integers, negated (B = -acc),
-    // shifted into B.  The constant of all limbs is removed with limb 0 (it must not survive into
-    // the next step's rotation: X^a * const != const).
-    auto recombine = [&](const cplx (&v)[8], auto LIc) __attribute__((always_inline)) {
-      constexpr int lr = decltype(LIc)::value;
-#pragma unroll
-      for (int m = 0; m < 8; ++m) {
-        const double tr = RND_MAGIC - v[m].re, ti = RND_MAGIC - v[m].im;
-        if constexpr (RESID) {
-          max_resid = fmax(max_resid, fabs(v[m].re - (RND_MAGIC - tr)));
-          max_resid = fmax(max_resid, fabs(v[m].im - (RND_MAGIC - ti)));
-        }
-        if constexpr (lr == 0) {
-          B[m] += (uint64_t)__double_as_longlong(tr) - MAGIC_ALL_3;
-          B[m + 8] += (uint64_t)__double_as_longlong(ti) - MAGIC_ALL_3;
-        } else {
-          B[m] += (uint64_t)__double_as_longlong(tr) << limb_shift(lr);
-          B[m + 8] += (uint64_t)__double_as_longlong(ti) << limb_shift(lr);
-        }
-      }
-    };
     static_for<0, LIMBS>([&](auto LI) __attribute__((always_inline)) {
       constexpr int li = decltype(LI)::value;
       cplx Ymine[4];
@@ -344,37 +288,25 @@ pbs1024_pair_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
         for (int ro = 0; ro < K1; ++ro) {
           const int r = (li * K1 + co) * K1 + ro;  // group within the step (constant)
           const bool last_step = i + 1 >= n;
-          if constexpr (STAMPS) {
-            uint64_t t = stamp();
-            acc_t[2] += t - tp;
-            tp = t;
-          }
+          lap(2);
           // group g landed for this wave's pieces (group g + 1 may stay in flight) ...
           if (r + 1 < NGRP || !last_step) wait_vmcnt<GLDS>();
           else wait_vmcnt<0>();
-          if constexpr (STAMPS) {
-            uint64_t t = stamp();
-            acc_t[8] += t - tp;
-            tp = t;
-          }
+          lap(8);
           // ... and for every wave's pieces; everyone is also done with group g - 1
 #ifndef DIAG_NOBAR
           pair_barrier();
 #endif
-          if constexpr (STAMPS) {
-            uint64_t t = stamp();
-            acc_t[5] += t - tp;
-            tp = t;
-          }
+          lap(5);
           // refill the slot of group g - 1 with group g + 2, right after the barrier (the DMA
           // needs the lead time: issued after the window's reads or FMAs it measured slower)
 #ifndef DIAG_NODMA
           if (r + 2 < NGRP) issue_group(key_step, r + 2);
           else if (!last_step) issue_group(key_step + PER_I, r + 2 - NGRP);
 #endif
-          if constexpr (FWD_LAST_VIA_WINDOW && li == 0) {
+          if constexpr (li == 0) {
             if (co == 0 && ro == 0) {
-              constexpr int QL = (L - 1) / FWD_XBATCH * FWD_XBATCH;  // first level of the last batch
+              constexpr int QL = (L - 1) / XB * XB;  // first level of the last batch
 #pragma unroll
               for (int q = QL; q < L; ++q)
 #pragma unroll
@@ -416,11 +348,7 @@ pbs1024_pair_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
           for (int j = 0; j < 4; ++j) partnermail[j * 64 + lane] = Y[j];
         }
       }
-      if constexpr (STAMPS) {
-        uint64_t t = stamp();
-        acc_t[2] += t - tp;
-        tp = t;
-      }
+      lap(2);
       xchg_barrier(pf, h, pcnt, guard);
       // my output polynomial's spectrum, slots in order k2 ^ 4h (undone by the inverse pass 1)
       cplx vp[8];
@@ -432,24 +360,17 @@ pbs1024_pair_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
       // no second sync: the only writes into my scratch by my partner are these Y mailboxes,
       // one per limb, always behind key-window workgroup barriers (the forward exchange only
       // reads the partner's scratch, under its own two syncs)
-      if constexpr (STAMPS) {
-        uint64_t t = stamp();
-        acc_t[3] += t - tp;
-        tp = t;
-      }
+      lap(3);
       cplx gi2[4];  // inverse pass-2 stage twiddles, read ahead of the transpose
       inv_p2_stage_tw(gi2, T, lane & 7);
       fft512_inv_tw(vp, xch, T, lane, gi2, hsign);
-      recombine(vp, LI);
+#pragma unroll
+      for (int m = 0; m < 8; ++m) recombine_one<li, RESID>(B[m], B[m + 8], vp[m], max_resid);
       // materialise B here (else the inverse tail sinks into the next limb's key windows)
 #pragma unroll
       for (int m = 0; m < 16; ++m) pin(B[m]);
       if constexpr (RESID) pin(max_resid);
-      if constexpr (STAMPS) {
-        uint64_t t = stamp();
-        acc_t[4] += t - tp;
-        tp = t;
-      }
+      lap(4);
     });
   }
 
@@ -498,7 +419,7 @@ pbs1024_pair_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
 // Key addressing (bsk.hip): group (limb, co, ro) holds at slot p < 4 column co / row ro and at
 // slot p >= 4 column 1 - co / row 1 - ro, so wave w reads (column c, row r) of its slot from group
 // (limb, c ^ f, r ^ f), f = (w >= 4): group index 2 c + r for f = 0, 3 - (2 c + r) for f = 1.
-// A step's 36 values are taken in the order t = (limb, c, level q, r) (SLOT_QMAJOR) through a ring of
+// A step's 36 values are taken in the order t = (limb, c, level q, r) through a ring of
 // SLOT_PF registers: value t + SLOT_PF is requested when value t has been used.
 //
 // Exchanges go through one 8 KB mailbox per wave (next to its transpose scratch):
@@ -507,7 +428,7 @@ pbs1024_pair_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
 //                        scratch (idle between transforms) | workgroup barrier | every wave reads
 //                        its slot from the 8 mailboxes and 8 scratches; the third transform, with
 //                        the first window's level-0/1 products (64 of its 96 FMAs) behind the
-//                        writes and reads of its LDS transpose (SLOT_L2_WINDOW); level 2 through
+//                        writes and reads of its LDS transpose; level 2 through
 //                        the mailbox alone | workgroup barrier | reads
 //   products, per limb:  Y[ct][co] -> mailbox of wave (ct, co) at position w | workgroup barrier |
 //                        the wave reads its 8 slots; limb li + 1's first product window; inverse
@@ -522,46 +443,9 @@ pbs1024_pair_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
 #ifndef SLOT_PF
 #define SLOT_PF 6  // key values in flight per wave (a divisor of 36; 6 = one (limb, output) window)
 #endif
-#ifndef SLOT_FWD_PAIR
-#define SLOT_FWD_PAIR 1  // forward levels 0 and 1 traded in one exchange (5 barriers per step): +1.4 %
-#endif
-#ifndef SLOT_Y_EARLY
-#define SLOT_Y_EARLY 1  // limb li + 1's first product window ahead of limb li's inverse: +3.2 %
-#endif
-#ifndef SLOT_QMAJOR
-#define SLOT_QMAJOR 1  // products of a window in (level, row) order instead of (row, level): +0.4 %
-#endif
-#ifndef SLOT_DEFAULT
-#define SLOT_DEFAULT 1  // the planned call's pair part runs the slot-split kernel
-#endif
-// Schedule stages of DESIGN.md §4.16, one switch each (each A/B-tested alone and on top of the
-// kept ones).  Figures: slowest run over the parent's fastest on the same box
-// (profiles/r11_slot/variants.json, which also holds the sub-variants that were measured and
-// deleted); the kernel sits at 256 VGPRs, and a stage that moves the register allocation moves
-// the time by more than the work it saves or hides.
-#ifndef SLOT_INV_FOLD
-#define SLOT_INV_FOLD 1  // the inverse's last twiddle psi^m and the rounding as two FMAs per part: alone -1.1 %, on SLOT_L2_WINDOW a gain
-#endif
-#ifndef SLOT_FWD_IL
-#define SLOT_FWD_IL 0  // forward levels 0 and 1 as one interleaved pair of transforms: -0.7 %
-#endif
-#ifndef SLOT_L2_WINDOW
-#define SLOT_L2_WINDOW 1  // first window's level-0/1 products inside the third transform's transpose: +1.75 %
-#endif
-#ifndef SLOT_INV_SPLIT
-#define SLOT_INV_SPLIT 0  // early window split around the inverse's pass 1 and transpose writes: -3.2 %
-#endif
-// SLOT_LANE_AGAIN: with SLOT_L2_WINDOW the lane index, needed again only by the sample extract,
-// is the one value spilled across the step loop; taking it again from mbcnt removes the spill.
-// The plain build has no spill with SLOT_INV_FOLD and loses 0.8 % to the recompute, so 1 applies
-// it to the RESID build only; without the fold every build needs it (2).
-#ifndef SLOT_LANE_AGAIN
-#define SLOT_LANE_AGAIN (SLOT_L2_WINDOW && !SLOT_INV_FOLD ? 2 : 1)
-#endif
-static_assert(!SLOT_FWD_IL || SLOT_FWD_PAIR, "the interleaved pair is traded in one exchange");
-static_assert(!SLOT_L2_WINDOW || (SLOT_Y_EARLY && SLOT_QMAJOR && SLOT_FWD_PAIR),
-              "the first window's first four products must need levels 0 and 1 only");
-static_assert(!SLOT_INV_SPLIT || SLOT_Y_EARLY, "the split window is the early one");
+// The schedule is the one stage-by-stage measurement kept (DESIGN.md §4.16,
+// profiles/r11_slot/variants.json): the kernel sits at 256 VGPRs, and a stage that moves the
+// register allocation moves the time by more than the work it saves or hides.
 // tan(pi m / 16), m = 0..7 (correctly rounded): psi^m = psi_pow(m).re * (1 + i psi_tan(m))
 __device__ __forceinline__ double psi_tan(int m) {
   constexpr double TAN[8] = {0.0,
@@ -626,7 +510,7 @@ pbs1024_pair_slot_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict_
   const int gstride = flip ? -GROUP : GROUP;
   auto key_load = [&](const cplx* key_step, int t) __attribute__((always_inline)) {
     const int li = t / (K1 * K1 * L), co = t / (K1 * L) % K1, e = t % (K1 * L);
-    const int ro = SLOT_QMAJOR ? e % K1 : e / L, q = SLOT_QMAJOR ? e / K1 : e % L, cr = co * K1 + ro;
+    const int ro = e % K1, q = e / K1, cr = co * K1 + ro;
     return (key_step + (li * K1 * K1 * GROUP + q * 512) + cr * gstride)[lane];
   };
   cplx g[PF] = {};
@@ -650,11 +534,7 @@ pbs1024_pair_slot_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict_
   {
     const uint32_t bt = active ? modswitch(lwe[n], LOG2_2N) : 0u;
 #pragma unroll
-    for (int m = 0; m < 16; ++m) {
-      const uint32_t src = (uint32_t)(lane + 64 * m + bt) & (2 * N - 1);
-      const uint64_t v = active ? lut[h * N + (src & (N - 1))] : 0ull;
-      B[m] = src < N ? 0ull - v : v;
-    }
+    for (int m = 0; m < 16; ++m) B[m] = neg_acc_coeff(lut, h, lane, m, bt, active);
   }
 
   const int nrep = 64 - L * (int)base_log;
@@ -693,24 +573,16 @@ pbs1024_pair_slot_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict_
     // ---- ct1 = B - X^{at} B and the decomposer state (pbs1024_pair_kernel)
     uint32_t st[16];
     {
-#pragma unroll
-      for (int m = 0; m < 16; ++m) xch64[lane + 64 * m] = B[m];
-      wave_lds_fence();
-      const uint32_t o0 = ((uint32_t)(lane - (int)at) << 3) + 8u * N;
-      const uint32_t khi = 1u << (nrep - 33);
+      acc_to_scratch(xch64, lane, B);
+      const uint32_t o0 = rot_o0(lane, at), khi = 1u << (nrep - 33);
+      // all 16 reads in flight at once (left to itself the scheduler issues them four at a time,
+      // one LDS round trip each)
       uint64_t rv[16];
 #pragma unroll
-      for (int m = 0; m < 16; ++m)
-        rv[m] = *reinterpret_cast<const uint64_t*>(reinterpret_cast<const char*>(xch64) + ((o0 + 512u * m) & 8191u));
+      for (int m = 0; m < 16; ++m) rv[m] = rot_read(xch64, o0, m);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int m = 0; m < 16; ++m) {
-        const uint32_t o = o0 + 512u * m;
-        const uint32_t s32 = (uint32_t)((int32_t)(o << 18) >> 31);
-        const uint64_t rvs = rv[m] ^ (((uint64_t)s32 << 32) | s32);
-        const uint64_t x = B[m] + rvs + (uint64_t)(s32 & 1u);
-        st[m] = ((uint32_t)(x >> 32) + khi) >> (nrep - 32);
-      }
+      for (int m = 0; m < 16; ++m) st[m] = rot_state(rot_term(rv[m], o0, m) + B[m], khi, nrep);
       wave_lds_fence();
     }
     lap(0);
@@ -720,13 +592,13 @@ pbs1024_pair_slot_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict_
     cplx X[L][NW];
     const int hi = lane >> 3, lo = lane & 7;
     // products e0 <= e < e1 of one window (output co of limb li for the 4 ciphertexts), in
-    // row-major (ro, q) order, or SLOT_QMAJOR: level-major (q, ro), which needs the last forward
-    // level's spectra only in the last third of a window.  Y is set by product 0 (no zeroing).
+    // level-major (q, ro) order, which needs the last forward level's spectra only in the last
+    // third of a window.  Y is set by product 0 (no zeroing).
     auto window_part = [&](cplx (&Y)[P], auto LIc, auto COc, auto E0c, auto E1c) __attribute__((always_inline)) {
       constexpr int li = decltype(LIc)::value, co = decltype(COc)::value;
 #pragma unroll
       for (int e = decltype(E0c)::value; e < decltype(E1c)::value; ++e) {
-        const int ro = SLOT_QMAJOR ? e % K1 : e / L, q = SLOT_QMAJOR ? e / K1 : e % L;
+        const int ro = e % K1, q = e / K1;
         const int t = (li * K1 + co) * K1 * L + e;
         const cplx gv = g[t % PF];
 #pragma unroll
@@ -757,10 +629,8 @@ pbs1024_pair_slot_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict_
     };
     constexpr std::integral_constant<int, 0> I0{};
     constexpr std::integral_constant<int, K1 * L> IE{};
-    // the first four products of a level-major window need levels 0 and 1 only, the first three
-    // are half of it
+    // the first four products of a level-major window need levels 0 and 1 only
     constexpr std::integral_constant<int, 2 * K1> IQ2{};
-    constexpr std::integral_constant<int, K1 * L / 2> IH{};
     auto window = [&](auto LIc, auto COc) __attribute__((always_inline)) {
       cplx Y[P];
       window_part(Y, LIc, COc, I0, IE);
@@ -774,66 +644,21 @@ pbs1024_pair_slot_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict_
 #pragma unroll
       for (int m = 0; m < 8; ++m) v[m] = {(double)d[m], (double)d[m + 8]};
     };
-    cplx Y0[P];  // SLOT_L2_WINDOW: window (limb 0, output 0), begun inside the third transform
-    (void)Y0;
-#if SLOT_FWD_IL
-    // Levels 0 and 1 as one interleaved pair: each transform's trip through the transpose scratch
-    // lies under the other's radix-8 pass.  One scratch serves both (a wave's LDS operations
-    // execute in issue order, and R2(0) is issued before W2(1)).
-    {
-      cplx v0[8], v1[8];
-      digits(v0, 0);
-      digits(v1, 1);
-      cplx tw2[4];
-      fwd_p2_tw(tw2, T, hi);
-      if (FWD_TW2_EARLY) __builtin_amdgcn_sched_barrier(0);
-      fwd_p1(v0);
-      fwd_p1(v1);
-      xpose_hi(v0);
-      xpose_hi(v1);
-      geo8<false>(v0, tw2);
-      fwd_w2(v0, xch, hi, lo);
-      wave_lds_fence();
-      // W2(0) | P2(1) | R2(0) W2(1) | P3(0) | R2(1) | P3(1)
-      slot_order();
-      geo8<false>(v1, tw2);
-      slot_order();
-      fwd_r2(v0, xch, hi, lo);
-      wave_lds_fence();
-      fwd_w2(v1, xch, hi, lo);
-      wave_lds_fence();
-      slot_order();
-      geo8<false>(v0, tw3);
-      slot_order();
-      fwd_r2(v1, xch, hi, lo);
-      wave_lds_fence();
-      geo8<false>(v1, tw3);
-      // level 0 to my mailbox, level 1 to my transpose scratch (idle between transforms)
+    cplx Y0[P];  // window (limb 0, output 0), begun inside the third transform
+    cplx hold[8];  // the level-0 spectrum during the second transform
 #pragma unroll
-      for (int k = 0; k < 8; ++k) mybox[k * 64] = v0[k], xch[k * 64 + lane] = v1[k];
-      lap(1);
-      pair_barrier();
-      lap(5);
-#pragma unroll
-      for (int u = 0; u < NW; ++u) X[0][u] = slotbox[u * MB], X[1][u] = xch_all[u * XS + w * 64 + lane];
-      slot_signal(ctr, lane, rcnt);
-    }
-#endif
-    cplx hold[8];  // SLOT_FWD_PAIR: the level-0 spectrum during the second transform
-    (void)hold;
-#pragma unroll
-    for (int q = SLOT_FWD_IL ? 2 : 0; q < L; ++q) {
+    for (int q = 0; q < L; ++q) {
       cplx v[8];
       digits(v, q);
       cplx tw2[4];
       fwd_p2_tw(tw2, T, hi);
-      if (FWD_TW2_EARLY) __builtin_amdgcn_sched_barrier(0);
-#if SLOT_FWD_PAIR
+      // issued here, ahead of pass 1 and the register transpose that hide their latency
+      __builtin_amdgcn_sched_barrier(0);
       // Levels 0 and 1 are traded in one exchange: level 0 waits in registers during the second
       // transform, then goes to my mailbox and level 1 to my transpose scratch (idle between
       // transforms).  The third transform overwrites that scratch, so it first waits (right
       // before its first LDS write) until every wave has read the pair.
-      if (SLOT_L2_WINDOW && q == 2) {
+      if (q == 2) {
         // the third transform with the first window's level-0/1 products behind its transpose's
         // writes and reads (the reads queue behind the writes: LDS operations of a wave execute
         // in issue order)
@@ -850,9 +675,7 @@ pbs1024_pair_slot_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict_
         slot_order();
         geo8<false>(v, tw3);
       } else {
-        fft512_fwd_tw(v, xch, lane, tw2, tw3, 0ull, [&]() __attribute__((always_inline)) {
-          if (q == 2) spin_until_ge(ctr, NW * rcnt, guard);
-        });
+        fft512_fwd_tw(v, xch, lane, tw2, tw3, 0ull, []() __attribute__((always_inline)) {});
       }
       if (q == 0) {
 #pragma unroll
@@ -873,25 +696,12 @@ pbs1024_pair_slot_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict_
         }
         slot_signal(ctr, lane, rcnt);
       }
-#else
-      fft512_fwd_tw(v, xch, lane, tw2, tw3, 0ull, []() __attribute__((always_inline)) {});
-      // every wave has read the previous level from my mailbox
-      if (q > 0) spin_until_ge(ctr, NW * rcnt, guard);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) mybox[k * 64] = v[k];
-      lap(1);
-      pair_barrier();
-      lap(5);
-#pragma unroll
-      for (int u = 0; u < NW; ++u) X[q][u] = slotbox[u * MB];
-      slot_signal(ctr, lane, rcnt);
-#endif
     }
     lap(1);
 
     // ---- per limb: products of my slot for the 4 ciphertexts and both outputs (key from
     //      registers, refilled PF values ahead), Y exchange, inverse of my polynomial.
-    // SLOT_INV_FOLD: v is the inverse's pass-3 output without its last twiddle conj(psi^m),
+    // recombine: v is the inverse's pass-3 output without its last twiddle conj(psi^m),
     // psi^m = c (1 + i t): v conj(psi^m) = c (u + i u'), u = re + t im, u' = im - t re, and the
     // product c u is rounded once, into the integer (RND_MAGIC - c u as one FMA).
     auto recombine = [&](const cplx (&v)[8], auto LIc) __attribute__((always_inline)) {
@@ -899,11 +709,11 @@ pbs1024_pair_slot_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict_
       // an FMA takes one scalar constant: the rounding constant goes through a vector register
       // pair, set here instead of held for the whole step loop
       double rnd = RND_MAGIC;
-      if (SLOT_INV_FOLD) pin(rnd);
+      pin(rnd);
 #pragma unroll
       for (int m = 0; m < 8; ++m) {
         double tr, ti;
-        if (SLOT_INV_FOLD && m > 0) {
+        if (m > 0) {
           // m > 4: psi^m = s (cot + i) with s = cos(pi (8 - m) / 16) and cot = tan(pi (8 - m) / 16),
           // the constants of 8 - m (no tangent above 1, 7 scalar constants in all: 13 spill SGPRs)
           const bool cot = m > 4;
@@ -926,31 +736,18 @@ pbs1024_pair_slot_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict_
             max_resid = fmax(max_resid, fabs(v[m].im - (RND_MAGIC - ti)));
           }
         }
-        if constexpr (lr == 0) {
-          B[m] += (uint64_t)__double_as_longlong(tr) - MAGIC_ALL_3;
-          B[m + 8] += (uint64_t)__double_as_longlong(ti) - MAGIC_ALL_3;
-        } else {
-          B[m] += (uint64_t)__double_as_longlong(tr) << limb_shift(lr);
-          B[m + 8] += (uint64_t)__double_as_longlong(ti) << limb_shift(lr);
-        }
+        limb_add<lr>(B[m], B[m + 8], tr, ti);
       }
     };
-    // SLOT_Y_EARLY: the first window of limb li + 1 runs between the reads of limb li's Y and its
-    // inverse, so the reads' latency (and the other waves' reads, which that window's mailbox
-    // writes wait for) is covered by 96 FMAs instead of being exposed right behind the barrier.
-    // SLOT_INV_SPLIT: that window is split around the inverse's pass 1 and transpose writes, so
-    // its second half covers the transpose's trip through LDS as well.
-    if (SLOT_L2_WINDOW) {
-      window_part(Y0, I0, I0, IQ2, IE);  // the level-2 products cover the rest of the X[2] reads
-      window_send(Y0, I0);
-    } else if (SLOT_Y_EARLY) {
-      window(I0, I0);
-    }
+    // The first window of limb li + 1 runs between the reads of limb li's Y and its inverse, so the
+    // reads' latency (and the other waves' reads, which that window's mailbox writes wait for) is
+    // covered by 96 FMAs instead of being exposed right behind the barrier.
+    window_part(Y0, I0, I0, IQ2, IE);  // the level-2 products cover the rest of the X[2] reads
+    window_send(Y0, I0);
     static_for<0, LIMBS>([&](auto LI) __attribute__((always_inline)) {
       constexpr int li = decltype(LI)::value;
       constexpr std::integral_constant<int, 1> I1{};
       constexpr std::integral_constant<int, li + 1> LN{};
-      if (!SLOT_Y_EARLY) window(LI, I0);
       window(LI, I1);
       lap(2);
       pair_barrier();
@@ -961,33 +758,16 @@ pbs1024_pair_slot_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict_
       slot_signal(ctr, lane, rcnt);
       lap(3);
       cplx gi2[4];  // inverse pass-2 stage twiddles, read ahead of the transpose
-      if constexpr (SLOT_INV_SPLIT && li + 1 < LIMBS) {
-        cplx Yn[P];
-        window_part(Yn, LN, I0, I0, IH);
-        slot_order();
-        inv_p1(vp, 0ull);
-        inv_w1(vp, xch, hi, lo);
-        wave_lds_fence();
-        slot_order();
-        window_part(Yn, LN, I0, IH, IE);
-        window_send(Yn, I0);
+      if constexpr (li + 1 < LIMBS) {
+        window(LN, I0);
         lap(2);
-        slot_order();
-        inv_p2_stage_tw(gi2, T, lo);
-        inv_r1(vp, xch, hi, lo);
-        wave_lds_fence();
-      } else {
-        if constexpr (SLOT_Y_EARLY && li + 1 < LIMBS) {
-          window(LN, I0);
-          lap(2);
-        }
-        inv_p2_stage_tw(gi2, T, lo);
-        inv_p1(vp, 0ull);
-        inv_w1(vp, xch, hi, lo);
-        wave_lds_fence();
-        inv_r1(vp, xch, hi, lo);
-        wave_lds_fence();
       }
+      inv_p2_stage_tw(gi2, T, lo);
+      inv_p1(vp, 0ull);
+      inv_w1(vp, xch, hi, lo);
+      wave_lds_fence();
+      inv_r1(vp, xch, hi, lo);
+      wave_lds_fence();
       {  // the rest of the inverse (fft512_inv_tw): pass 2, its output twiddles (read after the
          // transpose: their latency hides behind the butterflies), hi transpose, pass 3
         cplx t1[8];
@@ -997,8 +777,7 @@ pbs1024_pair_slot_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict_
 #pragma unroll
         for (int t = 0; t < 8; ++t) vp[t] = cmulc(vp[t], t1[t]);
         xpose_hi(vp);
-        if (SLOT_INV_FOLD) dft8<true>(vp);  // conj(psi^m) is applied by recombine
-        else inv_p3(vp);
+        dft8<true>(vp);  // pass 3 without its last twiddle: conj(psi^m) is applied by recombine
       }
       recombine(vp, LI);
       // materialise B here (else the inverse tail sinks into the next limb's products)
@@ -1017,11 +796,10 @@ pbs1024_pair_slot_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict_
     }
   }
 
-  // ---- sample extract (nth = 0) of acc = -B (pbs1024_pair_kernel).  SLOT_LANE_AGAIN: the lane index
-  //      is taken again (mbcnt of a full mask) instead of holding a register across the step loop.
-  const int lane_x = SLOT_LANE_AGAIN == 2 || (SLOT_LANE_AGAIN == 1 && RESID)
-                         ? (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u))
-                         : lane;
+  // ---- sample extract (nth = 0) of acc = -B (pbs1024_pair_kernel).  In the RESID build the lane
+  //      index, needed again only here, is the one value spilled across the step loop: it is taken
+  //      again (mbcnt of a full mask).  The plain build has no spill and loses 0.8 % to the recompute.
+  const int lane_x = RESID ? (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) : lane;
   uint64_t* o = out + (active ? (out_idx ? out_idx[s] : s) : 0) * (uint64_t)(K * N + 1);
   if (!active) {
   } else if (h == 0) {
@@ -1044,6 +822,20 @@ pbs1024_pair_slot_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict_
 // ------------------------------------------------------------------------------------
 // host launchers
 // ------------------------------------------------------------------------------------
+// An integer override from the environment, `unset` when absent.  Read per call: tests and A/B
+// runs switch CONCRETE_HIP_PBS_PAIRS / _QUAD / _HEX / _SLOT between calls.
+static int env_int(const char* name, int unset) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : unset;
+}
+// CONCRETE_HIP_PBS_STAMPS=1 (read once): the s_memtime-instrumented builds, with `resid` pointing at
+// NSTAMP u64 per wave of the grid (per-wave cycle sums)
+static bool env_set(const char* name) { return getenv(name) != nullptr; }
+static bool stamps_build() {
+  static const bool stamps = env_int("CONCRETE_HIP_PBS_STAMPS", 0) != 0;
+  return stamps;
+}
+
 template <bool RESID, bool STAMPS>
 static int launch_slot_t(const PbsArgs& a) {
   constexpr int P = PBS_PAIRS;
@@ -1059,8 +851,7 @@ static int launch_slot_t(const PbsArgs& a) {
 // the slot-split kernel (4 ciphertexts per workgroup, l = 3); with CONCRETE_HIP_PBS_STAMPS=1 its
 // instrumented build (`resid`: 8 * ceil(num_samples / 4) * NSTAMP u64)
 static int launch_slot(const PbsArgs& a) {
-  static const bool stamps = getenv("CONCRETE_HIP_PBS_STAMPS") && atoi(getenv("CONCRETE_HIP_PBS_STAMPS"));
-  if (stamps) return launch_slot_t<true, true>(a);
+  if (stamps_build()) return launch_slot_t<true, true>(a);
   return a.resid ? launch_slot_t<true, false>(a) : launch_slot_t<false, false>(a);
 }
 
@@ -1091,10 +882,8 @@ static uint32_t device_cus() {
 
 template <int P, int L>
 static int launch_pair_p(const PbsArgs& a) {
-  // diagnostic: CONCRETE_HIP_PBS_STAMPS=1 runs the s_memtime-instrumented build; `resid` must then
-  // point at 2 * P * ceil(num_samples / P) * NSTAMP u64 (per-wave cycle sums)
-  static const bool stamps = getenv("CONCRETE_HIP_PBS_STAMPS") && atoi(getenv("CONCRETE_HIP_PBS_STAMPS"));
-  if (stamps) return launch_pair_t<P, L, true, true>(a);
+  // stamps: `resid` holds 2 * P * ceil(num_samples / P) * NSTAMP u64
+  if (stamps_build()) return launch_pair_t<P, L, true, true>(a);
   return a.resid ? launch_pair_t<P, L, true, false>(a) : launch_pair_t<P, L, false, false>(a);
 }
 
@@ -1114,47 +903,38 @@ static PbsArgs pbs_args_range(const PbsArgs& a, uint32_t start, uint32_t count) 
 template <int L>
 static int launch_pair(const PbsArgs& a) {
   if (a.num_samples == 0) return 0;
-  // Ciphertexts per workgroup: a workgroup runs alone on its CU (LDS), so 4 per workgroup leaves
-  // CUs idle below 4 x CUs ciphertexts.  The round time of a workgroup falls with fewer waves per
-  // SIMD, but not in proportion: 2 per workgroup pays off while their workgroups fit one round
-  // (<= 2 x CUs ciphertexts), 1 per workgroup at <= CUs.  CONCRETE_HIP_PBS_PAIRS=1/2/4 forces it.
-  const char* fe = getenv("CONCRETE_HIP_PBS_PAIRS");  // read per call (tests switch it)
-  const int forced = fe ? atoi(fe) : 0;
+  // Dispatch (the measurements behind each rule: DESIGN.md §4.1, §4.11, §4.13, §4.16).  Overrides, each
+  // 0 = off, unset = automatic:
+  //   CONCRETE_HIP_PBS_SLOT=1         the slot kernel for the whole call (l = 3)
+  //   CONCRETE_HIP_PBS_HEX=1 / 2      the six-wave kernel, that many ciphertexts per workgroup (l = 3)
+  //   CONCRETE_HIP_PBS_QUAD=1 / 2     the four-wave kernel (l = 3, batches the ring kernel would run at
+  //                                   1 or 2 ciphertexts per workgroup)
+  //   CONCRETE_HIP_PBS_PAIRS=1 / 2 / 4  the ring kernel with that many ciphertexts per workgroup
+  // Automatic, l = 3, no PAIRS / QUAD override and no stamps: the call is split by pbs1024_plan.hpp into
+  // whole rounds of 4 x CUs ciphertexts for the slot kernel (SLOT=0: the ring kernel, the A/B switch),
+  // six-wave rounds of 2 x CUs and at most one round of one ciphertext per workgroup, each part a
+  // contiguous range of the batch on the caller's stream.
+  // Otherwise the ring kernel: a workgroup runs alone on its CU (LDS), so it takes 1 ciphertext per
+  // workgroup at <= CUs ciphertexts, 2 at <= 2 x CUs, else 4; at l = 3 and 1 per workgroup the
+  // four-wave kernel takes the call instead (QUAD=0 keeps the ring kernel).
+  const int forced = env_int("CONCRETE_HIP_PBS_PAIRS", 0);
+  const bool pairs_set = env_set("CONCRETE_HIP_PBS_PAIRS"), quad_set = env_set("CONCRETE_HIP_PBS_QUAD");
+  const bool stamps_set = env_set("CONCRETE_HIP_PBS_STAMPS");  // set at all, even to 0: no plan, no four-wave kernel
   const uint32_t cus = device_cus();
   const int P = forced == 1 || forced == 2 || forced == 4 ? forced
                 : a.num_samples <= cus ? 1 : a.num_samples <= 2 * cus ? 2 : 4;
-  // <= 1 ciphertext per CU at l = 3: four waves per ciphertext (pbs1024_quad.hip), +7 % at B = 256
-  // (at 2 per CU, B = 512, it measured 0.9x the pair kernel: DESIGN.md §4.1).  CONCRETE_HIP_PBS_QUAD=0
-  // keeps the pair kernel, =1 / =2 forces it with that many ciphertexts per workgroup (read per
-  // call: tests, A/B).
-  // Six waves per ciphertext (pbs1024_hex.hip, round 5), two ciphertexts per CU: a round of 2 x CUs
-  // ciphertexts takes ~5.41 ms against ~10.2 ms for the pair kernel's round of 4 x CUs (cfg2, one
-  // MI355X, profiles/r05/ab5_sweep.json), so it wins whenever it needs fewer than 1.886x the pair
-  // kernel's rounds — every batch of <= 2 x CUs (the metric's 512 per GPU on 8 GPUs: 92k vs 70k
-  // PBS/s), 1536, 2560 ... — and one ciphertext per workgroup at <= CUs (52.5k vs 40.6k at 256).
-  // CONCRETE_HIP_PBS_HEX=1 / =2 forces it with that many ciphertexts per workgroup, =0 keeps it off;
-  // a forced CONCRETE_HIP_PBS_PAIRS / _QUAD selects those kernels (read per call: tests, A/B).
-  // Round 6: the call is split over the kernels by pbs1024_plan.hpp (whole pair rounds, six-wave
-  // rounds, at most one round of one ciphertext per workgroup), each part a contiguous range of the
-  // batch launched on the caller's stream.
-  // The slot-split kernel (pbs1024_pair_slot_kernel): CONCRETE_HIP_PBS_SLOT=1 forces it for a whole
-  // call of any batch, =0 keeps the ring kernel in the plan's pair part (read per call: tests, A/B);
-  // unset, SLOT_DEFAULT decides.  Every other override keeps its meaning (CONCRETE_HIP_PBS_PAIRS=4 is
-  // the ring kernel: the A/B switch).
   if (L == 3) {
-    const char* se = getenv("CONCRETE_HIP_PBS_SLOT");
-    const int sl = se ? atoi(se) : -1;
+    const int sl = env_int("CONCRETE_HIP_PBS_SLOT", -1);
     if (sl == 1) return launch_slot(a);
-    const char* he = getenv("CONCRETE_HIP_PBS_HEX");
-    const int hx = he ? atoi(he) : -1;
+    const int hx = env_int("CONCRETE_HIP_PBS_HEX", -1);
     if (hx == 1 || hx == 2) return pbs1024_hex_launch(a, hx);
-    if (hx != 0 && !fe && !getenv("CONCRETE_HIP_PBS_QUAD") && !getenv("CONCRETE_HIP_PBS_STAMPS")) {
+    if (hx != 0 && !pairs_set && !quad_set && !stamps_set) {
       const Pbs1024Plan plan = plan_pbs1024(a.num_samples, cus);
       uint32_t start = 0;
       int rc = 0;
       if (plan.pair) {
         const PbsArgs part = pbs_args_range(a, start, plan.pair);
-        rc = (sl == 0 || !SLOT_DEFAULT) ? launch_pair_p<4, L>(part) : launch_slot(part);
+        rc = sl == 0 ? launch_pair_p<4, L>(part) : launch_slot(part);
         start += plan.pair;
       }
       if (rc == 0 && plan.hex2) {
@@ -1165,9 +945,8 @@ static int launch_pair(const PbsArgs& a) {
       return rc;
     }
   }
-  if (L == 3 && P <= 2 && !getenv("CONCRETE_HIP_PBS_STAMPS")) {
-    const char* qe = getenv("CONCRETE_HIP_PBS_QUAD");
-    const int q = qe ? atoi(qe) : -1;
+  if (L == 3 && P <= 2 && !stamps_set) {
+    const int q = env_int("CONCRETE_HIP_PBS_QUAD", -1);
     if (q == 1 || q == 2) return pbs1024_quad_launch(a, q);
     if (q != 0 && P == 1) return pbs1024_quad_launch(a, 1);
   }

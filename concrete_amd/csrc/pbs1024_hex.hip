@@ -50,9 +50,6 @@
 
 namespace chip {
 
-static_assert(MAGIC_ALL_3 == RND_MAGIC_BITS + (RND_MAGIC_BITS << 22) + (RND_MAGIC_BITS << 43),
-              "three limbs at shifts 0, 22, 43");
-
 // Sync group (kernel_util.hpp): the six waves of one ciphertext signal with group_signal<6> on its
 // counters and wait with spin_until_all_ge on the counters a phase depends on (all six, the three of
 // a polynomial, or the same wave of the other ciphertext).
@@ -97,11 +94,7 @@ pbs1024_hex_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_
   if (j == 0) {
     const uint32_t bt = active ? modswitch(lwe[n], LOG2_2N) : 0u;
 #pragma unroll
-    for (int m = 0; m < 16; ++m) {
-      const uint32_t src = (uint32_t)(lane + 64 * m + bt) & (2 * N - 1);
-      const uint64_t v = active ? lut[c * N + (src & (N - 1))] : 0ull;
-      accc[lane + 64 * m] = src < N ? 0ull - v : v;
-    }
+    for (int m = 0; m < 16; ++m) accc[lane + 64 * m] = neg_acc_coeff(lut, c, lane, m, bt, active);
   }
   uint32_t cnt = 0;
   __syncthreads();
@@ -175,20 +168,8 @@ pbs1024_hex_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_
     if (i + 1 < n) a_next = active ? lwe[i + 1] : 0ull;
     const uint32_t at = modswitch(ai, LOG2_2N);
 
-    // ---- ct1 = acc X^at - acc = B - X^at B of polynomial c (pbs1024_pair_kernel's offsets: bit 13
-    //      of o says "src < N", i.e. no wrap, where the rotated term is subtracted), decomposer state
-    const uint32_t o0 = ((uint32_t)(lane - (int)at) << 3) + 8u * N;
-    const char* accb = reinterpret_cast<const char*>(accc);
-    auto state_of = [&](uint64_t rv, uint64_t bv, int m) __attribute__((always_inline)) {
-      const uint32_t o = o0 + 512u * m;
-      const uint32_t s32 = (uint32_t)((int32_t)(o << 18) >> 31);
-      const uint64_t rvs = rv ^ (((uint64_t)s32 << 32) | s32);
-      const uint64_t x = bv + rvs + (uint64_t)(s32 & 1u);
-      return ((uint32_t)(x >> 32) + khi) >> (nrep - 32);
-    };
-    auto rot_read = [&](int m) __attribute__((always_inline)) {
-      return *reinterpret_cast<const uint64_t*>(accb + ((o0 + 512u * m) & 8191u));
-    };
+    // ---- ct1 = acc X^at - acc = B - X^at B of polynomial c (in LDS) and the decomposer state
+    const uint32_t o0 = rot_o0(lane, at);
     int32_t d[16];
     if constexpr (XM && HX_SHARED_DIGITS) {
       // Shared: wave (c, j) rotates and decomposes (every level) only the coefficient pairs
@@ -204,7 +185,7 @@ pbs1024_hex_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_
 #pragma unroll
           for (int hh = 0; hh < 2; ++hh) {
             const int m = MB + t + 8 * hh;
-            rv[hh][t] = rot_read(m);
+            rv[hh][t] = rot_read(accc, o0, m);
             bv[hh][t] = accc[lane + 64 * m];
           }
         __builtin_amdgcn_sched_barrier(0);
@@ -212,7 +193,8 @@ pbs1024_hex_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_
 #pragma unroll
         for (int t = 0; t < NM; ++t) {
           const int m = MB + t;
-          uint32_t s0 = state_of(rv[0][t], bv[0][t], m), s1 = state_of(rv[1][t], bv[1][t], m + 8);
+          uint32_t s0 = rot_state(bv[0][t] + rot_term(rv[0][t], o0, m), khi, nrep);
+          uint32_t s1 = rot_state(bv[1][t] + rot_term(rv[1][t], o0, m + 8), khi, nrep);
 #pragma unroll
           for (int q = 0; q < L; ++q) {
             const int32_t d0 = decomp_level32(s0, (uint32_t)(q * logB), logB, half_m1, neg_base, q + 1 < L);
@@ -239,12 +221,12 @@ pbs1024_hex_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_
         uint64_t rv[16], bv[16];
 #pragma unroll
         for (int m = 0; m < 16; ++m) {
-          rv[m] = rot_read(m);
+          rv[m] = rot_read(accc, o0, m);
           bv[m] = accc[lane + 64 * m];
         }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int m = 0; m < 16; ++m) st[m] = state_of(rv[m], bv[m], m);
+        for (int m = 0; m < 16; ++m) st[m] = rot_state(bv[m] + rot_term(rv[m], o0, m), khi, nrep);
       }
       lap(0);  // rotation + state
       // the levels up to mine (the lower ones only carry into it): one uniform branch around whole

@@ -26,9 +26,6 @@
 
 namespace chip {
 
-static_assert(MAGIC_ALL_3 == RND_MAGIC_BITS + (RND_MAGIC_BITS << 22) + (RND_MAGIC_BITS << 43),
-              "three limbs at shifts 0, 22, 43");
-
 // Sync groups (kernel_util.hpp): the four waves of one ciphertext (group_*<4> on its counters qf) and,
 // on separate counters pf, the two waves of one polynomial (group_sync<2> on pf + (v & 2)).
 template <int CTS, bool RESID>
@@ -96,11 +93,7 @@ pbs1024_quad_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
   {
     const uint32_t bt = active ? modswitch(lwe[n], LOG2_2N) : 0u;
 #pragma unroll
-    for (int m = 0; m < 16; ++m) {
-      const uint32_t src = (uint32_t)(lane + 64 * m + bt) & (2 * N - 1);
-      const uint64_t val = active ? lut[c * N + (src & (N - 1))] : 0ull;
-      B[m] = src < N ? 0ull - val : val;
-    }
+    for (int m = 0; m < 16; ++m) B[m] = neg_acc_coeff(lut, c, lane, m, bt, active);
   }
 
   const int nrep = 64 - L * (int)base_log;
@@ -114,20 +107,7 @@ pbs1024_quad_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
   auto recombine = [&](const cplx (&vv)[8], auto LIc) __attribute__((always_inline)) {
     constexpr int lr = decltype(LIc)::value;
 #pragma unroll
-    for (int m = 0; m < 8; ++m) {
-      const double tr = RND_MAGIC - vv[m].re, ti = RND_MAGIC - vv[m].im;
-      if constexpr (RESID) {
-        max_resid = fmax(max_resid, fabs(vv[m].re - (RND_MAGIC - tr)));
-        max_resid = fmax(max_resid, fabs(vv[m].im - (RND_MAGIC - ti)));
-      }
-      if constexpr (lr == 0) {
-        D[m] += (uint64_t)__double_as_longlong(tr) - MAGIC_ALL_3;
-        D[m + 8] += (uint64_t)__double_as_longlong(ti) - MAGIC_ALL_3;
-      } else {
-        D[m] += (uint64_t)__double_as_longlong(tr) << limb_shift(lr);
-        D[m + 8] += (uint64_t)__double_as_longlong(ti) << limb_shift(lr);
-      }
-    }
+    for (int m = 0; m < 8; ++m) recombine_one<lr, RESID>(D[m], D[m + 8], vv[m], max_resid);
   };
   auto inverse = [&](cplx (&vv)[8]) __attribute__((always_inline)) {
     cplx gi2[4];
@@ -143,27 +123,21 @@ pbs1024_quad_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
     if (i + 1 < n) a_next = active ? lwe[i + 1] : 0ull;
     const uint32_t at = modswitch(ai, LOG2_2N);
 
-    // ---- rotation and decomposer state in my own scratch (pbs1024_pair_kernel) ---------
+    // ---- rotation and decomposer state in my own scratch ---------------------------------
+    // (the scratch write stays a loop of this kernel, not acc_to_scratch: inside a helper its addresses
+    // take another form here and the listing moves, 213 -> 211 VGPRs at one ciphertext)
     uint32_t st[16];
     {
 #pragma unroll
       for (int m = 0; m < 16; ++m) xch64[lane + 64 * m] = B[m];
       wave_lds_fence();
-      const uint32_t o0 = ((uint32_t)(lane - (int)at) << 3) + 8u * N;
-      const uint32_t khi = 1u << (nrep - 33);
+      const uint32_t o0 = rot_o0(lane, at), khi = 1u << (nrep - 33);
       uint64_t rv[16];
 #pragma unroll
-      for (int m = 0; m < 16; ++m)
-        rv[m] = *reinterpret_cast<const uint64_t*>(reinterpret_cast<const char*>(xch64) + ((o0 + 512u * m) & 8191u));
+      for (int m = 0; m < 16; ++m) rv[m] = rot_read(xch64, o0, m);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int m = 0; m < 16; ++m) {
-        const uint32_t o = o0 + 512u * m;
-        const uint32_t s32 = (uint32_t)((int32_t)(o << 18) >> 31);
-        const uint64_t rvs = rv[m] ^ (((uint64_t)s32 << 32) | s32);
-        const uint64_t x = B[m] + rvs + (uint64_t)(s32 & 1u);
-        st[m] = ((uint32_t)(x >> 32) + khi) >> (nrep - 32);
-      }
+      for (int m = 0; m < 16; ++m) st[m] = rot_state(B[m] + rot_term(rv[m], o0, m), khi, nrep);
       wave_lds_fence();
     }
 

@@ -541,6 +541,50 @@ def test_pbs_pairs_per_workgroup(B, oracle, torch_cuda, monkeypatch, pairs, quad
     assert r < oracle.fft_error_bound(S.op, S.fbsk_cpu) < 0.5
 
 
+@pytest.fixture(scope="module")
+def edge_mask_case(B, oracle, torch_cuda):
+    """level -> (Setup, inputs, oracle result) of test_pbs_edge_masks_every_kernel, each made once and
+    released with the module."""
+    cases = {}
+
+    def case(level):
+        if level not in cases:
+            p = replace(B.CFG2, n=4, level=level, base_log=7)
+            S = Setup(B, oracle, torch_cuda, p, 8400 + level)
+            rng = np.random.RandomState(84 + level)
+            cts = encrypt(B, S, rng.randint(0, 4, size=8), 2, 8401 + level, std=2.0 ** -25)
+            words = np.array([0, (1 << 53) - 1, 1 << 63, (1 << 64) - 1], dtype=np.uint64)
+            for j in range(4):
+                cts[j, : p.n] = words[j]
+                cts[4 + j, : p.n] = np.roll(words, j)
+            accs = np.stack([lut_acc(B, S, rng.randint(0, 4, size=4), 2) for _ in range(8)])
+            lut_idx = np.arange(8, dtype=np.uint64)
+            cases[level] = (S, cts, accs, lut_idx, run_oracle(oracle, S, cts, accs, lut_idx=lut_idx))
+        return cases[level]
+
+    return case
+
+
+@pytest.mark.parametrize("env,level", [
+    ({"PAIRS": 1, "QUAD": 0}, 3), ({"PAIRS": 2, "QUAD": 0}, 3), ({"PAIRS": 4}, 3), ({"PAIRS": 4}, 1), ({"PAIRS": 4}, 2),
+    ({"QUAD": 1}, 3), ({"QUAD": 2}, 3), ({"HEX": 1}, 3), ({"HEX": 2}, 3)],
+    ids=lambda v: "-".join(f"{k}{x}" for k, x in v.items()) if isinstance(v, dict) else f"l{v}")
+def test_pbs_edge_masks_every_kernel(B, torch_cuda, monkeypatch, edge_mask_case, env, level):
+    """The rotation and decomposer state are one piece of code for the ring, four-wave and six-wave
+    kernels (kernel_util.hpp): each of them, forced by its override, on mask words set by hand — 0
+    (rotation by 0, the skip rule), 2^53 - 1 (just below a modulus-switch rounding boundary), 2^63
+    (rotation by N) and 2^64 - 1 (the largest round-up, to 2N = 0); one value per ciphertext in the
+    first four, all four mixed per step in the rest.  (The slot kernel has the same inputs in
+    test_gpu_pbs_slot_sched.py.)  PAIRS = 1 / 2 go with QUAD = 0, which keeps the ring kernel where the
+    four-wave kernel would take the call."""
+    for name, value in env.items():
+        monkeypatch.setenv("CONCRETE_HIP_PBS_" + name, str(value))
+    S, cts, accs, lut_idx, ref = edge_mask_case(level)
+    got = run_gpu(B, S, cts.copy(), accs.copy(), torch_cuda, lut_idx=lut_idx.copy())
+    assert B.device_status("cuda:0") == 0
+    assert np.array_equal(got, ref)
+
+
 @pytest.mark.parametrize("n_out,ks_l,ks_logB,nb", [(1024, 4, 3, 37), (1500, 4, 3, 37), (1500, 2, 11, 21),
                                                    (2100, 3, 4, 96), (1024, 4, 3, 80)])
 def test_keyswitch_wide_output_rows(B, oracle, torch_cuda, n_out, ks_l, ks_logB, nb):
