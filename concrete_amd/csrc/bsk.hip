@@ -161,16 +161,12 @@ __global__ void __launch_bounds__(256) convert_bsk_kernel(cplx* __restrict__ des
   }, smax);
 }
 
-// N = 2048, k = 1, l = 1 (pbs2048.hip).  Block = (i, limb, col, row, parity), in the order of
-// the output layout [n][limb][col][row][parity][512]: the parity half p(u) = g[2u + par] of key
-// polynomial g (row, col), limb `limb`, as an N = 1024 negacyclic polynomial: folded, twisted,
-// transformed exactly like the N = 1024 key.
-#if P2_PM
-// P2_PM: block = (i, limb, col, q, row); both parity spectra G_e, G_o in double-double, then the key
-// at the square roots of each evaluation point, K+-[f] = (G_e[f] +- s_f G_o[f]) / 2 with
+// N = 2048, k = 1 (pbs2048.hip).  Block = (i, limb, col, q, row).  The parity halves
+// p(u) = g[2u + par] of key polynomial g (row, col), limb `limb`, as N = 1024 negacyclic polynomials:
+// folded, twisted, transformed exactly like the N = 1024 key, both spectra G_e, G_o in double-double;
+// then the key at the square roots of each evaluation point, K+-[f] = (G_e[f] +- s_f G_o[f]) / 2 with
 // s_f = exp(i pi (1 - 4 f) / 2048) (s_f^2 = alpha_f), correctly rounded from double-double.  Layout
-// [n][limb][col][q][row][+-][slot][lane] (level v = l - 1 - q, q in digit order), scaled 1/512 like
-// the even/odd key.
+// [n][limb][col][q][row][+-][slot][lane] (level v = l - 1 - q, q in digit order), scaled 1/512.
 template <int LIMBS>
 __global__ void __launch_bounds__(256) convert_bsk2048_kernel(cplx* __restrict__ dest, const uint64_t* __restrict__ src,
                                                              const ddc* __restrict__ zeta_t,
@@ -214,33 +210,6 @@ __global__ void __launch_bounds__(256) convert_bsk2048_kernel(cplx* __restrict__
   }
   spec_max_commit(smax, m2);
 }
-#else
-template <int LIMBS>
-__global__ void __launch_bounds__(256) convert_bsk2048_kernel(cplx* __restrict__ dest, const uint64_t* __restrict__ src,
-                                                             const ddc* __restrict__ zeta_t,
-                                                             const ddc* __restrict__ tw_t, const ddc* __restrict__,
-                                                             uint32_t level, unsigned long long* smax) {
-  constexpr int M = 512, LOGM = 9;
-  __shared__ ddc buf[M];
-  const uint64_t blk = blockIdx.x;
-  const uint32_t par = (uint32_t)(blk & 1);
-  const uint32_t row = (uint32_t)((blk >> 1) & 1);
-  const uint32_t q = (uint32_t)((blk >> 2) % level);
-  const uint32_t col = (uint32_t)((blk >> 2) / level & 1);
-  const uint32_t limb = (uint32_t)(((blk >> 2) / level >> 1) % LIMBS);
-  const uint64_t i = ((blk >> 2) / level >> 1) / LIMBS;
-  const uint32_t v = level - 1 - q;
-  const uint64_t* g = src + ((i * level + v) * 4 + row * 2 + col) * 2048;  // [n][l][row][col][N]
-  for (int j = threadIdx.x; j < M; j += blockDim.x) {
-    ddc z{dd_from(limb_value<LIMBS>(g[2 * j + par], limb)), dd_from(limb_value<LIMBS>(g[2 * (j + M) + par], limb))};
-    z = ddc_mul(z, zeta_t[j]);
-    const int r = (int)(__builtin_bitreverse32((uint32_t)j) >> (32 - LOGM));
-    buf[r] = z;
-  }
-  __syncthreads();
-  dd_fft_scatter<M>(buf, tw_t, [&](int e) { return dest + blk * M + e; }, smax);
-}
-#endif
 
 // N = 1024, k = 2 (pbs1024k2.hip; l >= K2_MANY_MIN: level-major, [n][q][limb][col][row][512]).  Block = (i, limb, col, q, row), in the order of the
 // output layout [n][limb][col][q][row][512]: limb `limb` of key polynomial (row, col) of level
@@ -378,7 +347,7 @@ static void make_tables(uint32_t N, std::vector<ddc>& zeta, std::vector<ddc>& tw
     tw[t] = {{c.hi, c.lo}, {s.hi, s.lo}};
   }
 }
-// square roots s_f = exp(i pi (1 - 4 f) / 2048) of the N = 1024 evaluation points, f < 512 (P2_PM)
+// square roots s_f = exp(i pi (1 - 4 f) / 2048) of the N = 1024 evaluation points, f < 512
 static void make_sroots(std::vector<ddc>& sr) {
   const long double PI = 3.14159265358979323846264338327950288L;
   sr.resize(512);
@@ -416,7 +385,7 @@ int convert_bsk_launch(const ConvertArgs& a) {
     make_sroots(sr);
     CHIP_CHECK(hipMallocAsync((void**)&ds, sr.size() * sizeof(ddc), a.stream));
     CHIP_CHECK(hipMemcpyAsync(ds, sr.data(), sr.size() * sizeof(ddc), hipMemcpyHostToDevice, a.stream));
-    const uint64_t blocks = (uint64_t)a.n * PBS2_LIMBS * 4 * a.level * (P2_PM ? 1 : 2);
+    const uint64_t blocks = (uint64_t)a.n * PBS2_LIMBS * 4 * a.level;
     hipLaunchKernelGGL((convert_bsk2048_kernel<PBS2_LIMBS>), dim3((uint32_t)blocks), dim3(256), 0, a.stream,
                        reinterpret_cast<cplx*>(a.dest), a.src_dev, dz, dt, ds, a.level, a.smax);
     hipError_t e = hipGetLastError();

@@ -60,6 +60,11 @@ __device__ __forceinline__ cplx cmul(cplx a, cplx w) {
 __device__ __forceinline__ cplx cmulc(cplx a, cplx w) {
   return {__builtin_fma(a.re, w.re, a.im * w.im), __builtin_fma(a.im, w.re, -a.re * w.im)};
 }
+// acc += x * g, the re and im chains of two fused multiply-adds each (every key window)
+__device__ __forceinline__ void cfma(cplx& acc, const cplx& x, const cplx& g) {
+  acc.re = __builtin_fma(x.re, g.re, __builtin_fma(-x.im, g.im, acc.re));
+  acc.im = __builtin_fma(x.re, g.im, __builtin_fma(x.im, g.re, acc.im));
+}
 // a * (-i) (forward) or a * (+i) (inverse)
 template <bool INV>
 __device__ __forceinline__ cplx mul_mi(cplx a) {

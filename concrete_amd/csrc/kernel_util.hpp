@@ -2,7 +2,7 @@
 // pbs1024_hex.hip, pbs2048.hip, pbs1024k2.hip, pbs_small.hip, pbs512k4.hip) and by pbs_generic.hip /
 // keyswitch.hip: the wave-group sync on LDS counters and its bounded spin, the LDS-DMA issue of a
 // key-ring group, the limb rounding constants, the RESID epilogue and the step pieces
-// of the N = 1024, k = 1 family.
+// of the N = 1024, k = 1 family and of the 16-bit limb-grid family.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -38,8 +38,8 @@ constexpr int limb_shift(int li) { return li * 21 + (li > 0 ? 1 : 0); }
 constexpr uint64_t MAGIC_ALL_3 =
     (RND_MAGIC_BITS << limb_shift(0)) + (RND_MAGIC_BITS << limb_shift(1)) + (RND_MAGIC_BITS << limb_shift(2));
 
-// Workgroup barrier for the two waves of a ciphertext: LDS writes drained, compiler fence,
-// no vmcnt drain (key loads may stay in flight).
+// Workgroup barrier (two to eight waves, every ciphertext of the workgroup): LDS writes drained,
+// compiler fence, no vmcnt drain (key loads may stay in flight).
 __device__ __forceinline__ void pair_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // Bounded spin on an LDS counter: returns once *ctr >= target.  A wave that polls more than
@@ -262,5 +262,87 @@ __device__ __forceinline__ void recombine_one(uint64_t& are, uint64_t& aim, cons
     max_resid = fmax(max_resid, fabs(v.im - (RND_MAGIC - ti)));
   }
   limb_add<LR>(are, aim, tr, ti);
+}
+
+// ------------------------------------------------------------------------------------
+// 16-bit limb-grid family (pbs2048_quad_kernel, pbs1024k2_kernel, pbs1024k2_many_kernel,
+// pbs512k4_kernel, pbs512k4_many_kernel, pbs_small_kernel): the step pieces the six kernels share.
+// The key polynomial is split into LIMBS balanced limbs of LB bits (4 x 16; 5 x 13 at N = 512,
+// k = 4, l = 2); a wave holds 16 coefficients per lane of the accumulator acc itself (not negated).
+// ------------------------------------------------------------------------------------
+
+// Coefficient c of LUT_poly * X^{-bt}, bt = ms(b), in the ring of size N (blind_rotate_assign:
+// polynomial_wrapping_monic_monomial_div); 0 where `take` is false (a missing ciphertext, an empty
+// polynomial slot, a wave without accumulator).
+template <int N>
+__device__ __forceinline__ uint64_t acc_coeff(const uint64_t* lut, int poly, int c, uint32_t bt, bool take) {
+  const uint32_t src = (uint32_t)(c + bt) & (2 * N - 1);
+  const uint64_t val = take ? lut[poly * N + (src & (N - 1))] : 0ull;
+  return src < N ? val : 0ull - val;
+}
+
+// ---- ct1 = X^{at} acc - acc in the wave's own scratch: coefficient c reads acc[src & (N - 1)],
+//      src = c - at mod 2N, negated when src >= N.  rot_src: the index read; rot_coeff_state: the
+//      decomposer state (common.hpp decomp_init) of the coefficient from the value rv read there.
+template <int N>
+__device__ __forceinline__ uint32_t rot_src(int c, uint32_t at) {
+  return (uint32_t)(c - (int)at) & (N - 1);
+}
+template <class StT, int N>
+__device__ __forceinline__ StT rot_coeff_state(uint64_t rv, uint64_t a, int c, uint32_t at, int nrep) {
+  const uint32_t sp = (uint32_t)(c - (int)at) & (2 * N - 1);
+  return (StT)decomp_init((sp < N ? rv : 0ull - rv) - a, nrep);
+}
+
+// A digit d (logB <= 24) split exactly on the limb grid: d = lo + 2^16 hi with lo balanced 16-bit
+// (|lo| <= 2^15) and |hi| <= 2^(logB-17) + 1; d - lo is a multiple of 2^16, so the shift is exact.
+constexpr int SUB_BITS = 16;
+__device__ __forceinline__ void sub_digit_split(int32_t d, int32_t& lo, int32_t& hi) {
+  lo = ((d + (1 << (SUB_BITS - 1))) & ((1 << SUB_BITS) - 1)) - (1 << (SUB_BITS - 1));
+  hi = (d - lo) >> SUB_BITS;
+}
+
+// ---- key ring: the wait ahead of window r of a step of NGRP groups, until group r has landed for
+//      this wave's GLDS pieces.  steady: group r + DIST - 1 belongs to this step or a next step
+//      follows, so the next DIST - 1 groups may stay in flight; else this is the tail of the last
+//      step, where nothing more is issued.  The caller writes
+//      steady = r + DIST - 1 < NGRP || !last_step itself: evaluated in here, without the caller's
+//      short-circuit, it moves four kernels' listings.
+template <int GLDS, int DIST, class R>
+__device__ __forceinline__ void ring_wait(bool steady, R r, R ngrp) {
+  static_assert(DIST >= 1 && DIST <= 3, "vmcnt tail cases");
+  if (steady) wait_vmcnt<GLDS * (DIST - 1)>();
+  else if (r + 1 == ngrp) wait_vmcnt<0>();
+  else if (r + 2 == ngrp) wait_vmcnt<GLDS>();
+  else wait_vmcnt<GLDS * 2>();
+}
+
+// ---- rounding and recombination of limb li.  bits(v + MAGIC) = MAGIC_BITS + round(v): the limb's
+//      exact integers shifted into the accumulator at 2^{LB li}.  The constant of all limbs is
+//      removed with limb 0 (it must not survive into the next step's rotation: X^a * const != const).
+static_assert(limb_magic_all(4, 16) ==
+                  RND_MAGIC_BITS + (RND_MAGIC_BITS << 16) + (RND_MAGIC_BITS << 32) + (RND_MAGIC_BITS << 48),
+              "four 16-bit limbs");
+// tr, ti: the rounded parts x + RND_MAGIC
+template <int LB, int LIMBS>
+__device__ __forceinline__ void grid_limb_add(int li, uint64_t& are, uint64_t& aim, double tr, double ti) {
+  if (li == 0) {
+    are += (uint64_t)__double_as_longlong(tr) - limb_magic_all(LIMBS, LB);
+    aim += (uint64_t)__double_as_longlong(ti) - limb_magic_all(LIMBS, LB);
+  } else {
+    are += (uint64_t)__double_as_longlong(tr) << (LB * li);
+    aim += (uint64_t)__double_as_longlong(ti) << (LB * li);
+  }
+}
+// one complex value v of the inverse's output into the accumulators of its two coefficients
+template <int LB, int LIMBS, bool RESID>
+__device__ __forceinline__ void grid_recombine_one(int li, uint64_t& are, uint64_t& aim, const cplx& v,
+                                                   double& max_resid) {
+  const double tr = v.re + RND_MAGIC, ti = v.im + RND_MAGIC;
+  if constexpr (RESID) {
+    max_resid = fmax(max_resid, fabs(v.re - (tr - RND_MAGIC)));
+    max_resid = fmax(max_resid, fabs(v.im - (ti - RND_MAGIC)));
+  }
+  grid_limb_add<LB, LIMBS>(li, are, aim, tr, ti);
 }
 }  // namespace chip

@@ -32,8 +32,8 @@ constexpr int PBS2_CTS = 2;
 constexpr int PBS2_RING_SLOTS = 4;
 constexpr int PBS2_RING_DIST = 3;
 constexpr int PBS2_LIMBS = 4;     // 16-bit key limbs
-constexpr int PBS2_SUBS = 2;      // sub-digits per decomposition digit: balanced 16-bit d_lo, d_hi
-constexpr int PBS2_SUB_BITS = 16; // on the key-limb grid (pbs2048.hip)
+constexpr int PBS2_SUBS = 2;      // sub-digits per decomposition digit: balanced 16-bit d_lo, d_hi on the
+                                  // key-limb grid (kernel_util.hpp sub_digit_split)
 constexpr int PBS2_MAX_LOGB = 24; // |d_hi| <= 2^(logB-17) + 1 keeps the certified bound < 1/2
 // l = 2 .. PBS2_MAX_LEVEL: whole digits with l 2^(logB-1) <= 2^15 (the l = 1 digit's magnitude), the
 // levels' products summed into the same slot (the optimizer's 5-bit rows at br 2/15, 3/11, 4/9)
@@ -43,14 +43,11 @@ inline bool pbs2048_ok(uint32_t level, uint32_t base_log) {
   return level >= 2 && level <= PBS2_MAX_LEVEL && base_log >= 1 && base_log <= 15 &&
          ((uint64_t)level << (base_log - 1)) <= (1ull << 15);
 }
-// P2_PM = 1: the key holds the spectra at the two square roots +-s_k of each evaluation point
-// alpha_k, K+- = (G_e +- s G_o) / 2 (the N = 2048 polynomial evaluated at +-s_k, i.e. its
-// 1024-point negacyclic spectrum), so a product costs 2 complex multiplies per frequency instead
-// of the 4 of the even/odd form (a_e b_e + Z a_o b_o, a_e b_o + a_o b_e); 0: the even/odd key
-// (pbs2048.hip, bsk.hip; A/B builds only, the key format follows it).
-#ifndef P2_PM
-#define P2_PM 1
-#endif
+// The key holds the spectra at the two square roots +-s_k of each evaluation point alpha_k,
+// K+- = (G_e +- s G_o) / 2 (the N = 2048 polynomial evaluated at +-s_k, i.e. its 1024-point
+// negacyclic spectrum): a product costs 2 complex multiplies per frequency instead of the 4 of an
+// even/odd key (a_e b_e + Z a_o b_o, a_e b_o + a_o b_e), which is why this form was chosen
+// (pbs2048.hip, bsk.hip).
 constexpr size_t pbs2048_lds_bytes() {
   return PBS1024_TABLE_BYTES + 4 * PBS2_CTS * PBS1024_XCH_SLOTS * 16 + (size_t)PBS2_RING_SLOTS * 1024 * 16 +
          4 * PBS2_CTS * 4;  // + per-wave sync counters
@@ -63,7 +60,6 @@ constexpr int K2_CTS = 2;
 constexpr int K2_RING_SLOTS = 3;
 constexpr int K2_LIMBS = 4;
 constexpr int K2_SUBS = 2;
-constexpr int K2_SUB_BITS = 16;
 constexpr int K2_MAX_LOGB = 24;  // certified bound < 1/2 (oracle/pyoracle.py:gpu1024k2_error_bound)
 // l = 1: one digit split into two sub-digits (logB <= 24); l = 2: two whole digits with
 // l 2^(logB-1) <= 2^15 (the l = 1 digit's magnitude; the optimizer's br 2/15 rows), both levels'
@@ -72,10 +68,7 @@ constexpr uint32_t K2_MAX_LEVEL = 2;  // pbs1024k2_kernel's levels
 // l >= K2_MANY_MIN: one level at a time (pbs1024k2_many_kernel), the key level-major
 // ([n][q][limb][col][row][512]); whole digits with l 2^(logB-1) <= 2^15 and l logB < 64.  From l = 3
 // it is faster than holding every level's spectra (3.6 % at l = 3, profiles/r04manyab_rows.log).
-#ifndef K2_MANY_MIN_LEVEL
-#define K2_MANY_MIN_LEVEL 3
-#endif
-constexpr uint32_t K2_MANY_MIN = K2_MANY_MIN_LEVEL;
+constexpr uint32_t K2_MANY_MIN = 3;
 inline bool k2_ok(uint32_t level, uint32_t base_log) {
   if (level == 1) return base_log >= 1 && base_log <= (uint32_t)K2_MAX_LOGB;
   if (level >= K2_MANY_MIN && (uint64_t)level * base_log >= 64) return false;
@@ -96,7 +89,6 @@ constexpr size_t pbs1024k2_lds_bytes() {
 // and one output column: the k + 1 row spectra).  Key: 4 balanced 16-bit limbs, scaled 1 / (512 P).
 constexpr int SM_CTS = 4;
 constexpr int SM_LIMBS = 4;
-constexpr int SM_SUB_BITS = 16;
 // l = 2, 3: whole digits (l 2^(logB-1) <= 2^15, the l = 1, logB = 16 magnitude), the levels' products
 // summed into the same slot (the optimizer's rows at br 2/10, 2/12, 3/9)
 constexpr uint32_t SM_MAX_LEVEL = 3;
@@ -106,9 +98,7 @@ constexpr uint32_t SM_MAX_LEVEL = 3;
 inline uint32_t pbs_small_max_logb(uint32_t N) { return N == 512 || N == 256 ? 24u : 0u; }
 // key group = one limb and SM_GC(N) output columns (K1 row spectra each); SM_RS(N) ring slots
 // (two columns at N = 256 when k + 1 is even: half the key windows, 3 x 24 KB slots)
-#ifndef SM_GC256
-#define SM_GC256 2
-#endif
+constexpr int SM_GC256 = 2;
 constexpr int sm_gc(int N, int K1) { return N == 256 && K1 % SM_GC256 == 0 ? SM_GC256 : 1; }
 constexpr int sm_rs(int N, int K1) { return sm_gc(N, K1) == 2 ? 3 : 4; }
 constexpr size_t pbs_small_lds_bytes(int N, int K1) {
@@ -128,10 +118,7 @@ constexpr uint32_t K4_MAX_LEVEL = 2;  // pbs512k4_kernel's levels (l = 2: 13-bit
 // l >= K4_MANY_MIN: one level at a time (pbs512k4_many_kernel), the key level-major
 // ([n][q][limb][col][row][M]); whole digits with l 2^(logB-1) <= 2^15 and l logB < 64.  From l = 3
 // it is faster than holding every level's spectra (3-7 % at l = 3 .. 5, profiles/r04manyab_rows.log).
-#ifndef K4_MANY_MIN_LEVEL
-#define K4_MANY_MIN_LEVEL 3
-#endif
-constexpr uint32_t K4_MANY_MIN = K4_MANY_MIN_LEVEL;
+constexpr uint32_t K4_MANY_MIN = 3;
 constexpr size_t pbs512k4_lds_bytes() {
   return PBS1024_TABLE_BYTES + 3 * K4_CTS * PBS1024_XCH_SLOTS * 16 + (size_t)K4_RING_SLOTS * 5 * 256 * 16 +
          4 * K4_CTS * 4 * 2 + 4 * 64 * 16;  // + sync counters (padded to 16 B) + the many-level kernel's tz

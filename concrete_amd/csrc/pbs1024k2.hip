@@ -39,20 +39,8 @@ namespace chip {
 
 namespace {
 
-static_assert(limb_magic_all(4, 16) ==
-                  RND_MAGIC_BITS + (RND_MAGIC_BITS << 16) + (RND_MAGIC_BITS << 32) + (RND_MAGIC_BITS << 48),
-              "four 16-bit limbs");
-
 // first frequency slot of wave v's share (v = 0, 1, 2; SB(3) = 8)
-#ifndef K2_SB1
-#define K2_SB1 3
-#endif
-#ifndef K2_SB2
-#define K2_SB2 5
-#endif
-#ifndef K2_ASM_DMA
-#define K2_ASM_DMA 0
-#endif
+constexpr int K2_SB1 = 3, K2_SB2 = 5;
 // Diagnostic builds only (timing; wrong results): K2D_NOBAR (no key-window barriers), K2D_NOMAC
 // (no key MAC FMAs), K2D_NOINV / K2D_NOFWD (no inverse / forward transforms), K2D_NOTRI (no
 // three-wave syncs).
@@ -147,8 +135,7 @@ pbs1024k2_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_id
   cplx* ring_w = ring + w * GLDS * 64;
   const uint32_t lane_b = (uint32_t)lane * (uint32_t)sizeof(cplx);
   auto issue_group = [&](const cplx* key_step, int r) __attribute__((always_inline)) {
-    ring_issue<GLDS, K2_ASM_DMA != 0>(reinterpret_cast<const char*>(key_step + r * GROUP), ring_w + (r % RS) * GROUP,
-                                      lane_b);
+    ring_issue<GLDS, false>(reinterpret_cast<const char*>(key_step + r * GROUP), ring_w + (r % RS) * GROUP, lane_b);
   };
   if (n > 0) {
 #pragma unroll
@@ -169,11 +156,7 @@ pbs1024k2_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_id
   {
     const uint32_t bt = active ? modswitch(lwe[n], LOG2_2N) : 0u;
 #pragma unroll
-    for (int m = 0; m < 16; ++m) {
-      const uint32_t src = (uint32_t)(lane + 64 * m + bt) & (2 * N - 1);
-      const uint64_t val = active ? lut[v * N + (src & (N - 1))] : 0ull;
-      A[m] = src < N ? val : 0ull - val;
-    }
+    for (int m = 0; m < 16; ++m) A[m] = acc_coeff<N>(lut, v, lane + 64 * m, bt, active);
   }
 
   const int nrep = 64 - NQ * (int)base_log;
@@ -198,13 +181,10 @@ pbs1024k2_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_id
       wave_lds_fence();
       uint64_t rv[16];
 #pragma unroll
-      for (int m = 0; m < 16; ++m) rv[m] = K2D_NOROT ? A[m] ^ at : xch64[(uint32_t)(lane + 64 * m - (int)at) & (N - 1)];
+      for (int m = 0; m < 16; ++m) rv[m] = K2D_NOROT ? A[m] ^ at : xch64[rot_src<N>(lane + 64 * m, at)];
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int m = 0; m < 16; ++m) {
-        const uint32_t sp = (uint32_t)(lane + 64 * m - (int)at) & (2 * N - 1);
-        st[m] = (StT)decomp_init((sp < N ? rv[m] : 0ull - rv[m]) - A[m], nrep);
-      }
+      for (int m = 0; m < 16; ++m) st[m] = rot_coeff_state<StT, N>(rv[m], A[m], lane + 64 * m, at, nrep);
       wave_lds_fence();
     }
 
@@ -219,9 +199,7 @@ pbs1024k2_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_id
         dlo[m] = d;                           // level q = 0 (least significant first)
         dhi[m] = decomp_next_t(st[m], logB);  // level q = 1
       } else {
-        const int32_t lo = ((d + (1 << (K2_SUB_BITS - 1))) & ((1 << K2_SUB_BITS) - 1)) - (1 << (K2_SUB_BITS - 1));
-        dlo[m] = lo;
-        dhi[m] = (d - lo) >> K2_SUB_BITS;  // exact: d - lo is a multiple of 2^16
+        sub_digit_split(d, dlo[m], dhi[m]);
       }
     }
 #pragma unroll
@@ -286,8 +264,7 @@ pbs1024k2_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_id
         for (int cc = 0; cc < K1; ++cc) {
           const int r = li * K1 + cc;  // group within the step
           // group r landed for this wave's pieces (the next DIST - 1 may stay in flight) ...
-          if (r + DIST - 1 < NGRP || !last_step) wait_vmcnt<GLDS * (DIST - 1)>();
-          else wait_vmcnt<0>();
+          ring_wait<GLDS, DIST>(r + DIST - 1 < NGRP || !last_step, r, NGRP);
           if (!K2D_NOBAR) pair_barrier();  // ... for every wave; everyone is done with group r - 1
           // refill the slot of group r - 1 with group r + DIST (RS = DIST + 1)
           if (r + DIST < NGRP) issue_group(key_step, r + DIST);
@@ -314,14 +291,8 @@ pbs1024k2_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_id
 #pragma unroll
             for (int jj = 0; jj < (K2D_NOMAC ? 0 : MS); ++jj) {
               if (has(jj)) {
-                const cplx x0 = X[row][0][jj];
-                Ya[jj].re = __builtin_fma(x0.re, g[jj].re, __builtin_fma(-x0.im, g[jj].im, Ya[jj].re));
-                Ya[jj].im = __builtin_fma(x0.re, g[jj].im, __builtin_fma(x0.im, g[jj].re, Ya[jj].im));
-                if constexpr (HI) {
-                  const cplx x1 = X[row][1][jj];
-                  Yn[cc][jj].re = __builtin_fma(x1.re, g[jj].re, __builtin_fma(-x1.im, g[jj].im, Yn[cc][jj].re));
-                  Yn[cc][jj].im = __builtin_fma(x1.re, g[jj].im, __builtin_fma(x1.im, g[jj].re, Yn[cc][jj].im));
-                }
+                cfma(Ya[jj], X[row][0][jj], g[jj]);
+                if constexpr (HI) cfma(Yn[cc][jj], X[row][1][jj], g[jj]);
               }
             }
           }
@@ -353,8 +324,7 @@ pbs1024k2_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_id
 #pragma unroll
           for (int q = 0; q < NQ; ++q) {
             const int r = (li * K1 + cc) * NQ + q;  // group within the step
-            if (r + DIST - 1 < NGRP || !last_step) wait_vmcnt<GLDS * (DIST - 1)>();
-            else wait_vmcnt<0>();
+            ring_wait<GLDS, DIST>(r + DIST - 1 < NGRP || !last_step, r, NGRP);
             if (!K2D_NOBAR) pair_barrier();
             if (r + DIST < NGRP) issue_group(key_step, r + DIST);
             else if (!last_step) issue_group(key_step + PER_I, r + DIST - NGRP);
@@ -376,11 +346,7 @@ pbs1024k2_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_id
                 if (has(jj)) g[jj] = G[row * 512 + jj * 64];
 #pragma unroll
               for (int jj = 0; jj < MS; ++jj) {
-                if (has(jj)) {
-                  const cplx x = X[row][q][jj];
-                  Ya[jj].re = __builtin_fma(x.re, g[jj].re, __builtin_fma(-x.im, g[jj].im, Ya[jj].re));
-                  Ya[jj].im = __builtin_fma(x.re, g[jj].im, __builtin_fma(x.im, g[jj].re, Ya[jj].im));
-                }
+                if (has(jj)) cfma(Ya[jj], X[row][q][jj], g[jj]);
               }
             }
 #pragma unroll
@@ -401,20 +367,7 @@ pbs1024k2_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_id
         if (!K2D_NOINV) fft512_inv_tw(V, xch, T, lane, gi2, 0);
       }
 #pragma unroll
-      for (int m = 0; m < 8; ++m) {
-        const double tr = V[m].re + RND_MAGIC, ti = V[m].im + RND_MAGIC;
-        if constexpr (RESID) {
-          max_resid = fmax(max_resid, fabs(V[m].re - (tr - RND_MAGIC)));
-          max_resid = fmax(max_resid, fabs(V[m].im - (ti - RND_MAGIC)));
-        }
-        if constexpr (li == 0) {
-          A[m] += (uint64_t)__double_as_longlong(tr) - limb_magic_all(K2_LIMBS, 16);
-          A[m + 8] += (uint64_t)__double_as_longlong(ti) - limb_magic_all(K2_LIMBS, 16);
-        } else {
-          A[m] += (uint64_t)__double_as_longlong(tr) << (16 * li);
-          A[m + 8] += (uint64_t)__double_as_longlong(ti) << (16 * li);
-        }
-      }
+      for (int m = 0; m < 8; ++m) grid_recombine_one<16, K2_LIMBS, RESID>(li, A[m], A[m + 8], V[m], max_resid);
       // materialise A here (else the inverse tail sinks into the next limb's key windows)
 #pragma unroll
       for (int m = 0; m < 16; ++m) pin(A[m]);
@@ -441,11 +394,6 @@ pbs1024k2_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_id
   }
 
   if constexpr (RESID) report_resid(max_resid, lane, active, resid_out);
-}
-
-template <bool RESID, int NQ>
-static int launch_k2_t(const PbsArgs& a) {
-  return launch_fused(pbs1024k2_kernel<RESID, NQ>, K2_CTS, K2_CTS * 192, pbs1024k2_lds_bytes(), a);
 }
 
 // Many levels (l >= K2_MANY_MIN, runtime), whole digits, one level at a time (as
@@ -519,11 +467,7 @@ pbs1024k2_many_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ o
   {
     const uint32_t bt = active ? modswitch(lwe[n], LOG2_2N) : 0u;
 #pragma unroll
-    for (int m = 0; m < 16; ++m) {
-      const uint32_t src = (uint32_t)(lane + 64 * m + bt) & (2 * N - 1);
-      const uint64_t val = active && owner ? lut[v * N + (src & (N - 1))] : 0ull;
-      A[m] = src < N ? val : 0ull - val;
-    }
+    for (int m = 0; m < 16; ++m) A[m] = acc_coeff<N>(lut, v, lane + 64 * m, bt, active && owner);
   }
 
   const int nrep = 64 - (int)level * (int)base_log;
@@ -545,13 +489,10 @@ pbs1024k2_many_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ o
       wave_lds_fence();
       uint64_t rv[16];
 #pragma unroll
-      for (int m = 0; m < 16; ++m) rv[m] = xch64[(uint32_t)(lane + 64 * m - (int)at) & (N - 1)];
+      for (int m = 0; m < 16; ++m) rv[m] = xch64[rot_src<N>(lane + 64 * m, at)];
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int m = 0; m < 16; ++m) {
-        const uint32_t sp = (uint32_t)(lane + 64 * m - (int)at) & (2 * N - 1);
-        st[m] = decomp_init((sp < N ? rv[m] : 0ull - rv[m]) - A[m], nrep);
-      }
+      for (int m = 0; m < 16; ++m) st[m] = rot_coeff_state<uint64_t, N>(rv[m], A[m], lane + 64 * m, at, nrep);
       wave_lds_fence();
     }
 
@@ -588,7 +529,7 @@ pbs1024k2_many_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ o
       for (int wi = 0; wi < WPL; ++wi) {
         const int li = wi / K1, cc = wi % K1;
         const uint32_t r = q * (uint32_t)WPL + (uint32_t)wi;
-        if (issuer) {
+        if (issuer) {  // ring_wait's ladder, written out: through the helper this kernel spills two more SGPRs
           if (r + DIST - 1 < NGRP || !last_step) wait_vmcnt<GLDS * (DIST - 1)>();
           else if (r + 1 == NGRP) wait_vmcnt<0>();
           else if (r + 2 == NGRP) wait_vmcnt<GLDS>();
@@ -607,10 +548,7 @@ pbs1024k2_many_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ o
         for (int row = 0; row < K1; ++row) {
 #pragma unroll
           for (int jj = 0; jj < MS; ++jj) {
-            const cplx g = G[row * 512 + jj * 64];
-            cplx& y = Y[li][cc][jj];
-            y.re = __builtin_fma(X[row][jj].re, g.re, __builtin_fma(-X[row][jj].im, g.im, y.re));
-            y.im = __builtin_fma(X[row][jj].re, g.im, __builtin_fma(X[row][jj].im, g.re, y.im));
+            cfma(Y[li][cc][jj], X[row][jj], G[row * 512 + jj * 64]);
           }
         }
 #pragma unroll
@@ -636,20 +574,7 @@ pbs1024k2_many_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ o
           fft512_inv_tw(V, xch, T, lane, gi2, 0);
         }
 #pragma unroll
-        for (int m = 0; m < 8; ++m) {
-          const double tr = V[m].re + RND_MAGIC, ti = V[m].im + RND_MAGIC;
-          if constexpr (RESID) {
-            max_resid = fmax(max_resid, fabs(V[m].re - (tr - RND_MAGIC)));
-            max_resid = fmax(max_resid, fabs(V[m].im - (ti - RND_MAGIC)));
-          }
-          if (li == 0) {
-            A[m] += (uint64_t)__double_as_longlong(tr) - limb_magic_all(K2_LIMBS, 16);
-            A[m + 8] += (uint64_t)__double_as_longlong(ti) - limb_magic_all(K2_LIMBS, 16);
-          } else {
-            A[m] += (uint64_t)__double_as_longlong(tr) << (16 * li);
-            A[m + 8] += (uint64_t)__double_as_longlong(ti) << (16 * li);
-          }
-        }
+        for (int m = 0; m < 8; ++m) grid_recombine_one<16, K2_LIMBS, RESID>(li, A[m], A[m + 8], V[m], max_resid);
 #pragma unroll
         for (int m = 0; m < 16; ++m) pin(A[m]);
       } else {
@@ -679,23 +604,17 @@ pbs1024k2_many_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ o
   if constexpr (RESID) report_resid(max_resid, lane, active, resid_out);
 }
 
-template <bool RESID>
-static int launch_k2_many_t(const PbsArgs& a) {
-  return launch_fused(pbs1024k2_many_kernel<RESID>, K2_CTS, K2_CTS * 256, pbs1024k2_many_lds_bytes(), a);
-}
-
 int pbs1024k2_launch(const PbsArgs& a) {
-  if (!(a.N == 1024 && a.k == 2 && a.limbs == (uint32_t)K2_LIMBS && k2_ok(a.level, a.base_log))) {
-    set_error("unsupported PBS parameters: N=%u k=%u level=%u base_log=%u limbs=%u", a.N, a.k, a.level, a.base_log,
-              a.limbs);
-    return -2;
-  }
+  if (!(a.N == 1024 && a.k == 2 && a.limbs == (uint32_t)K2_LIMBS && k2_ok(a.level, a.base_log)))
+    return reject_params(a);
   if (a.num_samples == 0) return 0;
-  if (a.level >= K2_MANY_MIN) return a.resid ? launch_k2_many_t<true>(a) : launch_k2_many_t<false>(a);
-  switch (a.level) {
-    case 1: return a.resid ? launch_k2_t<true, 1>(a) : launch_k2_t<false, 1>(a);
-    default: return a.resid ? launch_k2_t<true, 2>(a) : launch_k2_t<false, 2>(a);
-  }
+  return with_resid(a, [&](auto R) {
+    constexpr bool RESID = decltype(R)::value;
+    if (a.level >= K2_MANY_MIN)
+      return launch_fused(pbs1024k2_many_kernel<RESID>, K2_CTS, K2_CTS * 256, pbs1024k2_many_lds_bytes(), a);
+    if (a.level == 1) return launch_fused(pbs1024k2_kernel<RESID, 1>, K2_CTS, K2_CTS * 192, pbs1024k2_lds_bytes(), a);
+    return launch_fused(pbs1024k2_kernel<RESID, 2>, K2_CTS, K2_CTS * 192, pbs1024k2_lds_bytes(), a);
+  });
 }
 
 }  // namespace chip

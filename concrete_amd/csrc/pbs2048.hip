@@ -25,7 +25,7 @@
 // of the frequencies, trades quarters back and runs the inverse transforms of its own output.
 // PBS2_CTS ciphertexts per workgroup share a ring of 16 KB key groups filled by LDS-DMA.
 //
-// Products at the square roots (P2_PM, pbs.hpp).  With s_k^2 = alpha_k, the N = 2048 polynomial
+// Products at the square roots (pbs.hpp).  With s_k^2 = alpha_k, the N = 2048 polynomial
 // evaluated at +-s_k is A+-_k = A_e(alpha_k) +- s_k A_o(alpha_k) (its 1024-point negacyclic
 // spectrum: the even/odd 512-point transforms plus one radix-2 stage), so
 //     C+- = A+- B+-,   C_e = (C+ + C-) / 2,   C_o = (C+ - C-) / (2 s_k)
@@ -42,10 +42,6 @@
 #include <type_traits>
 
 namespace chip {
-
-static_assert(limb_magic_all(4, 16) ==
-                  RND_MAGIC_BITS + (RND_MAGIC_BITS << 16) + (RND_MAGIC_BITS << 32) + (RND_MAGIC_BITS << 48),
-              "four 16-bit limbs");
 
 // Diagnostic builds only (timing, wrong results): D4_NOBAR (no key-window barriers), D4_NOMAC
 // (no key MAC FMAs), D4_NOINV (no inverse transforms), D4_NOFWD (no forward transforms),
@@ -66,12 +62,6 @@ static_assert(limb_magic_all(4, 16) ==
 #define D4_NOQS 0
 #endif
 
-#ifndef P2_DEFER_INV
-#define P2_DEFER_INV 1  // limb li's inverse after limb li + 1's first key-window barrier, no quad sync (+1.0 %)
-#endif
-#ifndef P2_SPLIT_XSYNC
-#define P2_SPLIT_XSYNC 1  // split second sync of the sub-0 exchange (+1.1 %)
-#endif
 // Sync group (kernel_util.hpp group_*<4>): the four waves of one ciphertext, qf = its counters;
 // group_sync<2> on qf + (v & 2) joins the two parity waves of one polynomial only.
 __device__ __forceinline__ void quad_sync(uint32_t* qf, int v, uint32_t& cnt, const SyncGuard& guard) {
@@ -149,14 +139,9 @@ pbs2048_quad_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
   {
     const uint32_t bt = active ? modswitch(lwe[n], LOG2_2N) : 0u;
 #pragma unroll
-    for (int m = 0; m < 16; ++m) {
-      const uint32_t src = (uint32_t)(2 * (lane + 64 * m) + par + bt) & (2 * N - 1);
-      const uint64_t val = active ? lut[c * N + (src & (N - 1))] : 0ull;
-      A[m] = src < N ? val : 0ull - val;
-    }
+    for (int m = 0; m < 16; ++m) A[m] = acc_coeff<N>(lut, c, 2 * (lane + 64 * m) + par, bt, active);
   }
 
-#if P2_PM
   // square roots s_k = exp(i pi (1 - 4k) / 2048) of the evaluation points of my two frequency slots
   cplx sroot[2];
 #pragma unroll
@@ -179,18 +164,6 @@ pbs2048_quad_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
         X[2 * row + 1][sub][jj] = csub(xe, so);
       }
   };
-#else
-  // evaluation points of my two frequency slots (multiplication by Z = X^2)
-  cplx alpha[2];
-#pragma unroll
-  for (int jj = 0; jj < 2; ++jj) {
-    const int k = fft512_freq(lane, 2 * v + jj);
-    const int num = (1 - 4 * k) & 2047;  // in units of pi / 1024
-    double sn, cs;
-    sincospi((double)num / 1024.0, &sn, &cs);
-    alpha[jj] = {cs, sn};
-  }
-#endif
 
   const int nrep = 64 - NQ * (int)base_log;
   const int logB = (int)base_log;
@@ -243,9 +216,7 @@ pbs2048_quad_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
 #pragma unroll
       for (int m = 0; m < 16; ++m) {
         const int32_t d = decomp_next_t(st[m], logB);
-        const int32_t lo = ((d + (1 << (PBS2_SUB_BITS - 1))) & ((1 << PBS2_SUB_BITS) - 1)) - (1 << (PBS2_SUB_BITS - 1));
-        dlo[m] = lo;
-        dhi[m] = (d - lo) >> PBS2_SUB_BITS;  // exact: d - lo is a multiple of 2^16
+        sub_digit_split(d, dlo[m], dhi[m]);
       }
     }
 #pragma unroll
@@ -259,7 +230,6 @@ pbs2048_quad_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
 #pragma unroll
         for (int m = 0; m < 8; ++m)
           vv8[m] = sub == 0 || NQ > 1 ? cplx{(double)dlo[m], (double)dlo[m + 8]} : cplx{(double)dhi[m], (double)dhi[m + 8]};
-#if P2_SPLIT_XSYNC
         if (!D4_NOFWD) {
           cplx tw2[4], tw3[4];
           fwd_p2_tw(tw2, T, lane >> 3);
@@ -270,9 +240,6 @@ pbs2048_quad_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
             if (sub > 0) group_wait<4>(qf, v, qcnt, guard);
           });
         }
-#else
-        if (!D4_NOFWD) fft512_fwd(vv8, xch, T, lane);
-#endif
 #pragma unroll
         for (int k2 = 0; k2 < 8; ++k2) xch[k2 * 64 + lane] = vv8[k2];
       }
@@ -285,28 +252,25 @@ pbs2048_quad_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
         for (int vv = 0; vv < 4; ++vv)
 #pragma unroll
           for (int jj = 0; jj < 2; ++jj) X[vv][sub][jj] = ctx[vv * XS + (2 * v + jj) * 64 + lane];
-#if P2_PM
         to_pm(X, sub);
-#endif
 #pragma unroll
         for (int vv = 0; vv < 4; ++vv)
 #pragma unroll
           for (int jj = 0; jj < 2; ++jj) pin(X[vv][sub][jj]);
       }
       // everyone has read my spectrum before my next transform writes the scratch; after the
-      // last sub-digit the scratches are next written behind the key windows' barriers
-#if P2_SPLIT_XSYNC
+      // last sub-digit the scratches are next written behind the key windows' barriers (the wait
+      // for this signal sits in the next transform: +1.1 % over a second full sync here)
       if (sub + 1 < NF) group_signal<4>(qf, v, qcnt);
-#else
-      if (sub + 1 < NF) quad_sync(qf, v, qcnt, guard);
-#endif
     }
 
     // ---- per limb: MAC for the four outputs on my quarter, trade quarters, inverse ---------
-    // Slot li = sum over rows of d_lo * g_li + d_hi * g_{li-1}: Ya/Pa hold slot li (its d_hi part
-    // from the previous limb's windows), Yb/Pb start slot li + 1 with d_hi * g_li.  Y[cc][par][jj]:
-    // output (column cc, parity par) at my frequency slot 2v + jj; P: the odd x odd products, times
-    // alpha when the slot is folded (after its windows: once for the d_hi part, once for d_lo).
+    // Slot li = sum over rows of d_lo * g_li + d_hi * g_{li-1}: Ya holds slot li (its d_hi part
+    // from the previous limb's windows), Yb starts slot li + 1 with d_hi * g_li.  Y[cc][pm][jj]:
+    // U+ (pm = 0) / U- (pm = 1) of output column cc at my frequency slot 2v + jj.
+    // Pa / Pb: zeros that are only pinned, never read (what is left of an even/odd product form).
+    // The pins cost a v_mov_b64 each per window, and without them every instantiation's listing moves
+    // (and <RESID, NQ = 3> goes from 251 to 255 VGPRs), so they go only with a timed change.
     cplx Ya[2][2][2], Pa[2][2];
 #pragma unroll
     for (int cc = 0; cc < 2; ++cc)
@@ -327,20 +291,7 @@ pbs2048_quad_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
         fft512_inv_tw(V, xch, T, lane, gi2, 0);
       }
 #pragma unroll
-      for (int m = 0; m < 8; ++m) {
-        const double tr = V[m].re + RND_MAGIC, ti = V[m].im + RND_MAGIC;
-        if constexpr (RESID) {
-          max_resid = fmax(max_resid, fabs(V[m].re - (tr - RND_MAGIC)));
-          max_resid = fmax(max_resid, fabs(V[m].im - (ti - RND_MAGIC)));
-        }
-        if constexpr (lj == 0) {
-          A[m] += (uint64_t)__double_as_longlong(tr) - limb_magic_all(PBS2_LIMBS, 16);
-          A[m + 8] += (uint64_t)__double_as_longlong(ti) - limb_magic_all(PBS2_LIMBS, 16);
-        } else {
-          A[m] += (uint64_t)__double_as_longlong(tr) << (16 * lj);
-          A[m + 8] += (uint64_t)__double_as_longlong(ti) << (16 * lj);
-        }
-      }
+      for (int m = 0; m < 8; ++m) grid_recombine_one<16, PBS2_LIMBS, RESID>(lj, A[m], A[m + 8], V[m], max_resid);
       // materialise A here (else the inverse tail sinks into the next limb's key windows)
 #pragma unroll
       for (int m = 0; m < 16; ++m) pin(A[m]);
@@ -360,30 +311,12 @@ pbs2048_quad_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
       for (int cc = 0; cc < 2; ++cc)
 #pragma unroll
         for (int jj = 0; jj < 2; ++jj) Yb[cc][0][jj] = Yb[cc][1][jj] = Pb[cc][jj] = {0.0, 0.0};
-#if P2_PM
-      // U+ += A+ K+, U- += A- K- of one row (Y[0] / Y[1] hold U+ / U-; P unused)
-      auto mac = [&](cplx (&Y)[2][2], cplx (&P)[2], const cplx& xp, const cplx& xm, const cplx& kp, const cplx& km,
+      // U+ += A+ K+, U- += A- K- of one row (Y[0] / Y[1] hold U+ / U-)
+      auto mac = [&](cplx (&Y)[2][2], const cplx& xp, const cplx& xm, const cplx& kp, const cplx& km,
                      int jj) __attribute__((always_inline)) {
-        (void)P;
-        Y[0][jj].re = __builtin_fma(xp.re, kp.re, __builtin_fma(-xp.im, kp.im, Y[0][jj].re));
-        Y[0][jj].im = __builtin_fma(xp.re, kp.im, __builtin_fma(xp.im, kp.re, Y[0][jj].im));
-        Y[1][jj].re = __builtin_fma(xm.re, km.re, __builtin_fma(-xm.im, km.im, Y[1][jj].re));
-        Y[1][jj].im = __builtin_fma(xm.re, km.im, __builtin_fma(xm.im, km.re, Y[1][jj].im));
+        cfma(Y[0][jj], xp, kp);
+        cfma(Y[1][jj], xm, km);
       };
-#else
-      // (a_e b_e + Z a_o b_o) and (a_e b_o + a_o b_e) of one row into (Y, P)
-      auto mac = [&](cplx (&Y)[2][2], cplx (&P)[2], const cplx& xe, const cplx& xo, const cplx& ge, const cplx& go,
-                     int jj) __attribute__((always_inline)) {
-        Y[0][jj].re = __builtin_fma(xe.re, ge.re, __builtin_fma(-xe.im, ge.im, Y[0][jj].re));
-        Y[0][jj].im = __builtin_fma(xe.re, ge.im, __builtin_fma(xe.im, ge.re, Y[0][jj].im));
-        P[jj].re = __builtin_fma(xo.re, go.re, __builtin_fma(-xo.im, go.im, P[jj].re));
-        P[jj].im = __builtin_fma(xo.re, go.im, __builtin_fma(xo.im, go.re, P[jj].im));
-        Y[1][jj].re = __builtin_fma(xe.re, go.re, __builtin_fma(-xe.im, go.im, Y[1][jj].re));
-        Y[1][jj].im = __builtin_fma(xe.re, go.im, __builtin_fma(xe.im, go.re, Y[1][jj].im));
-        Y[1][jj].re = __builtin_fma(xo.re, ge.re, __builtin_fma(-xo.im, ge.im, Y[1][jj].re));
-        Y[1][jj].im = __builtin_fma(xo.re, ge.im, __builtin_fma(xo.im, ge.re, Y[1][jj].im));
-      };
-#endif
 #pragma unroll
       for (int cc = 0; cc < K1; ++cc) {
 #pragma unroll
@@ -391,15 +324,14 @@ pbs2048_quad_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
           const int q = rq / K1, row = rq % K1;  // level (NQ > 1), row
           const int r = (li * K1 + cc) * K1 * NQ + rq;  // group within the step
           // group r landed for this wave's pieces (the next DIST - 1 may stay in flight) ...
-          if (r + DIST - 1 < NGRP || !last_step) wait_vmcnt<GLDS * (DIST - 1)>();
-          else if (r + 1 == NGRP) wait_vmcnt<0>();
-          else if (r + 2 == NGRP) wait_vmcnt<GLDS>();
-          else wait_vmcnt<GLDS * 2>();
+          ring_wait<GLDS, DIST>(r + DIST - 1 < NGRP || !last_step, r, NGRP);
           if (!D4_NOBAR) pair_barrier();  // ... for every wave; everyone is done with group r - 1
           // refill the slot of group r - 1 with group r + DIST (RS = DIST + 1)
           if (r + DIST < NGRP) issue_group(key_step, r + DIST);
           else if (!last_step) issue_group(key_step + PER_I, r + DIST - NGRP);
-          if constexpr (P2_DEFER_INV && li > 0) {
+          // limb li - 1's inverse, deferred to behind this limb's first key-window barrier (which
+          // publishes the mailboxes as a quad sync would: +1.0 %)
+          if constexpr (li > 0) {
             if (cc == 0 && rq == 0) inverse_limb(std::integral_constant<int, li - 1>{});
           }
           if constexpr (li == 0) {
@@ -409,9 +341,7 @@ pbs2048_quad_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
 #pragma unroll
                 for (int jj = 0; jj < 2; ++jj)
                   X[vv][NF - 1][jj] = ctx[vv * XS + (2 * v + jj) * 64 + lane];
-#if P2_PM
               to_pm(X, NF - 1);
-#endif
             }
           }
           {
@@ -423,11 +353,11 @@ pbs2048_quad_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
             // them one at a time, each behind its own LDS round trip): +1.1 %, 255 VGPRs
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int jj = 0; jj < (D4_NOMAC ? 0 : 2); ++jj) mac(Ya[cc], Pa[cc], X[2 * row][q][jj], X[2 * row + 1][q][jj], ge[jj], go[jj], jj);
+            for (int jj = 0; jj < (D4_NOMAC ? 0 : 2); ++jj) mac(Ya[cc], X[2 * row][q][jj], X[2 * row + 1][q][jj], ge[jj], go[jj], jj);
             if constexpr (HI) {
 #pragma unroll
               for (int jj = 0; jj < (D4_NOMAC ? 0 : 2); ++jj)
-                mac(Yb[cc], Pb[cc], X[2 * row][1][jj], X[2 * row + 1][1][jj], ge[jj], go[jj], jj);
+                mac(Yb[cc], X[2 * row][1][jj], X[2 * row + 1][1][jj], ge[jj], go[jj], jj);
             }
             // this window's products are done here, not sunk past the next window's barrier
 #pragma unroll
@@ -437,46 +367,34 @@ pbs2048_quad_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
             }
           }
         }
-        // column cc of slot li is complete: fold Z a_o b_o in and send my quarter of outputs
+        // column cc of slot li is complete: unfold it and send my quarter of outputs
         // vo = 2 cc + par straight into wave vo's mailbox, slot pair (v, jj).  Every scratch has been
         // idle since this limb's first key-window barrier (the last sub-digit's spectra were read
         // before the second), and nobody writes it again before the next limb's windows.
 #pragma unroll
         for (int jj = 0; jj < 2; ++jj) {
-#if P2_PM
           // C_e = U+ + U-, C_o = (U+ - U-) conj(s)
           const cplx ce = cadd(Ya[cc][0][jj], Ya[cc][1][jj]);
           const cplx co = cmulc(csub(Ya[cc][0][jj], Ya[cc][1][jj]), sroot[jj]);
           ctxw[(2 * cc) * XS + (v * 2 + jj) * 64 + lane] = ce;
           ctxw[(2 * cc + 1) * XS + (v * 2 + jj) * 64 + lane] = co;
-#else
-          Ya[cc][0][jj] = cadd(Ya[cc][0][jj], cmul(Pa[cc][jj], alpha[jj]));
-          ctxw[(2 * cc) * XS + (v * 2 + jj) * 64 + lane] = Ya[cc][0][jj];
-          ctxw[(2 * cc + 1) * XS + (v * 2 + jj) * 64 + lane] = Ya[cc][1][jj];
-#endif
         }
       }
-      // slot li + 1 so far (d_hi * g_li): fold its odd products now, so that only the Y values are
-      // carried across the inverse; the next limb's d_lo products restart P from zero
+      // slot li + 1 so far (d_hi * g_li) is carried into the next limb's windows
       if constexpr (HI) {
 #pragma unroll
         for (int cc = 0; cc < 2; ++cc)
 #pragma unroll
           for (int jj = 0; jj < 2; ++jj) {
-#if P2_PM
             Ya[cc][0][jj] = Yb[cc][0][jj];
-#else
-            Ya[cc][0][jj] = cadd(Yb[cc][0][jj], cmul(Pb[cc][jj], alpha[jj]));
-#endif
             Ya[cc][1][jj] = Yb[cc][1][jj];
             Pa[cc][jj] = {0.0, 0.0};
             pin(Ya[cc][0][jj]), pin(Ya[cc][1][jj]);
           }
       }
       // limb li's outputs are in the mailboxes: its inverse runs here for the last limb, and for the
-      // others after the next limb's first key-window barrier (P2_DEFER_INV), which publishes the
-      // mailboxes as this quad sync does
-      if constexpr (!P2_DEFER_INV || li + 1 == PBS2_LIMBS) {
+      // others after the next limb's first key-window barrier (above)
+      if constexpr (li + 1 == PBS2_LIMBS) {
         quad_sync(qf, v, qcnt, guard);
         inverse_limb(LI);
       }
@@ -506,24 +424,20 @@ pbs2048_quad_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out
   if constexpr (RESID) report_resid(max_resid, lane, active, resid_out);
 }
 
-template <bool RESID, int NQ>
-static int launch2048_t(const PbsArgs& a) {
-  return launch_fused(pbs2048_quad_kernel<RESID, NQ>, PBS2_CTS, PBS2_CTS * 256, pbs2048_lds_bytes(), a);
-}
-
 int pbs2048_launch(const PbsArgs& a) {
-  if (!(a.N == 2048 && a.k == 1 && a.limbs == (uint32_t)PBS2_LIMBS && pbs2048_ok(a.level, a.base_log))) {
-    set_error("unsupported PBS parameters: N=%u k=%u level=%u base_log=%u limbs=%u", a.N, a.k, a.level, a.base_log,
-              a.limbs);
-    return -2;
-  }
+  if (!(a.N == 2048 && a.k == 1 && a.limbs == (uint32_t)PBS2_LIMBS && pbs2048_ok(a.level, a.base_log)))
+    return reject_params(a);
   if (a.num_samples == 0) return 0;
-  switch (a.level) {
-    case 1: return a.resid ? launch2048_t<true, 1>(a) : launch2048_t<false, 1>(a);
-    case 2: return a.resid ? launch2048_t<true, 2>(a) : launch2048_t<false, 2>(a);
-    case 3: return a.resid ? launch2048_t<true, 3>(a) : launch2048_t<false, 3>(a);
-    default: return a.resid ? launch2048_t<true, 4>(a) : launch2048_t<false, 4>(a);
-  }
+  return with_resid(a, [&](auto R) {
+    constexpr bool RESID = decltype(R)::value;
+    auto launch = [&](auto kern) { return launch_fused(kern, PBS2_CTS, PBS2_CTS * 256, pbs2048_lds_bytes(), a); };
+    switch (a.level) {
+      case 1: return launch(pbs2048_quad_kernel<RESID, 1>);
+      case 2: return launch(pbs2048_quad_kernel<RESID, 2>);
+      case 3: return launch(pbs2048_quad_kernel<RESID, 3>);
+      default: return launch(pbs2048_quad_kernel<RESID, 4>);
+    }
+  });
 }
 
 }  // namespace chip

@@ -5,7 +5,23 @@
 #include "fft512.hpp"
 #include "pbs.hpp"
 
+#include <type_traits>
+
 namespace chip {
+
+// what every fused launcher answers to a parameter set outside its gate
+inline int reject_params(const PbsArgs& a) {
+  set_error("unsupported PBS parameters: N=%u k=%u level=%u base_log=%u limbs=%u", a.N, a.k, a.level, a.base_log,
+            a.limbs);
+  return -2;
+}
+
+// f(std::true_type) when the caller asked for the rounding residual (the kernels' RESID builds), else
+// f(std::false_type)
+template <class F>
+int with_resid(const PbsArgs& a, F&& f) {
+  return a.resid ? f(std::true_type{}) : f(std::false_type{});
+}
 
 // Launches `kern` on ceil(num_samples / cts) workgroups of `threads` threads with `lds` bytes of
 // dynamic LDS.  Every fused kernel takes (out, out_idx, luts, lut_idx, in, in_idx, fbsk, n, base_log,

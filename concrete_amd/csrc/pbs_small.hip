@@ -51,10 +51,6 @@ namespace chip {
 
 namespace {
 
-static_assert(limb_magic_all(4, 16) ==
-                  RND_MAGIC_BITS + (RND_MAGIC_BITS << 16) + (RND_MAGIC_BITS << 32) + (RND_MAGIC_BITS << 48),
-              "four 16-bit limbs");
-
 // P-point DFTs over the slots of one lane: unzip F_p = sum_q w_P^{-pq} Y_q, zip Y_q = sum_p w_P^{pq} F_p
 // (w_P = exp(-2 pi i / P), unnormalised)
 template <int P>
@@ -181,9 +177,7 @@ pbs_small_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_id
 #pragma unroll
     for (int m = 0; m < 16; ++m) {
       const int c = jb + (64 / P) * (m & 7) + (m >= 8 ? M : 0);
-      const uint32_t src = (uint32_t)(c + bt) & (2 * N - 1);
-      const uint64_t val = active && real ? lut[pa * N + (src & (N - 1))] : 0ull;
-      A[m] = src < N ? val : 0ull - val;
+      A[m] = acc_coeff<N>(lut, pa, c, bt, active && real);
     }
   }
 
@@ -209,14 +203,13 @@ pbs_small_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_id
 #pragma unroll
       for (int m = 0; m < 16; ++m) {
         const int c = jb + (64 / P) * (m & 7) + (m >= 8 ? M : 0);
-        rv[m] = xch64[pl * N + ((uint32_t)(c - (int)at) & (N - 1))];
+        rv[m] = xch64[pl * N + rot_src<N>(c, at)];
       }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int m = 0; m < 16; ++m) {
         const int c = jb + (64 / P) * (m & 7) + (m >= 8 ? M : 0);
-        const uint32_t sp = (uint32_t)(c - (int)at) & (2 * N - 1);
-        st[m] = (StT)decomp_init((sp < N ? rv[m] : 0ull - rv[m]) - A[m], nrep);
+        st[m] = rot_coeff_state<StT, N>(rv[m], A[m], c, at, nrep);
       }
       wave_lds_fence();
     }
@@ -227,12 +220,7 @@ pbs_small_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_id
     int32_t dd[SUBS][16];  // SUBS = 2: both sub-digits; else the current level's digits
     if constexpr (SUBS == 2) {
 #pragma unroll
-      for (int m = 0; m < 16; ++m) {
-        const int32_t d = decomp_next_t(st[m], logB);
-        const int32_t lo = ((d + (1 << (SM_SUB_BITS - 1))) & ((1 << SM_SUB_BITS) - 1)) - (1 << (SM_SUB_BITS - 1));
-        dd[0][m] = lo;
-        dd[1][m] = (d - lo) >> SM_SUB_BITS;
-      }
+      for (int m = 0; m < 16; ++m) sub_digit_split(decomp_next_t(st[m], logB), dd[0][m], dd[1][m]);
     }
 #pragma unroll
     for (int sub = 0; sub < NF; ++sub) {
@@ -297,11 +285,7 @@ pbs_small_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_id
 #pragma unroll
         for (int cg = 0; cg < NCG; ++cg) {
           const int r = li * NCG + cg;
-          static_assert(DIST <= 3, "vmcnt tail cases");
-          if (r + DIST - 1 < NGRP || !last_step) wait_vmcnt<GLDS * (DIST - 1)>();
-          else if (r + 1 == NGRP) wait_vmcnt<0>();
-          else if (r + 2 == NGRP) wait_vmcnt<GLDS>();
-          else wait_vmcnt<GLDS * 2>();
+          ring_wait<GLDS, DIST>(r + DIST - 1 < NGRP || !last_step, r, NGRP);
           pair_barrier();
           if (r + DIST < NGRP) issue_group(key_step, r + DIST);
           else if (!last_step) issue_group(key_step + PER_I, r + DIST - NGRP);
@@ -328,14 +312,8 @@ pbs_small_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_id
             for (int js = 0; js < MS; ++js) g[js] = G[row * M + js * 64];
 #pragma unroll
             for (int js = 0; js < (SMD_NOMAC ? 0 : MS); ++js) {
-              const cplx x0 = X[row][0][js];
-              Ya[js].re = __builtin_fma(x0.re, g[js].re, __builtin_fma(-x0.im, g[js].im, Ya[js].re));
-              Ya[js].im = __builtin_fma(x0.re, g[js].im, __builtin_fma(x0.im, g[js].re, Ya[js].im));
-              if constexpr (HI) {
-                const cplx x1 = X[row][SUBS - 1][js];
-                Yn[cc][js].re = __builtin_fma(x1.re, g[js].re, __builtin_fma(-x1.im, g[js].im, Yn[cc][js].re));
-                Yn[cc][js].im = __builtin_fma(x1.re, g[js].im, __builtin_fma(x1.im, g[js].re, Yn[cc][js].im));
-              }
+              cfma(Ya[js], X[row][0][js], g[js]);
+              if constexpr (HI) cfma(Yn[cc][js], X[row][SUBS - 1][js], g[js]);
             }
           }
           // column cc of slot li: my slots into its owner's mailbox (each wave only ever touches its
@@ -367,10 +345,7 @@ pbs_small_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_id
 #pragma unroll
           for (int q = 0; q < NQ; ++q) {
             const int r = (li * NCG + cg) * NQ + q;
-            if (r + DIST - 1 < NGRP || !last_step) wait_vmcnt<GLDS * (DIST - 1)>();
-            else if (r + 1 == NGRP) wait_vmcnt<0>();
-            else if (r + 2 == NGRP) wait_vmcnt<GLDS>();
-            else wait_vmcnt<GLDS * 2>();
+            ring_wait<GLDS, DIST>(r + DIST - 1 < NGRP || !last_step, r, NGRP);
             pair_barrier();
             if (r + DIST < NGRP) issue_group(key_step, r + DIST);
             else if (!last_step) issue_group(key_step + PER_I, r + DIST - NGRP);
@@ -390,10 +365,7 @@ pbs_small_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_id
               for (int row = 0; row < K1; ++row) {
 #pragma unroll
                 for (int js = 0; js < MS; ++js) {
-                  const cplx g = G[row * M + js * 64];
-                  const cplx x = X[row][q][js];
-                  Ya[c2][js].re = __builtin_fma(x.re, g.re, __builtin_fma(-x.im, g.im, Ya[c2][js].re));
-                  Ya[c2][js].im = __builtin_fma(x.re, g.im, __builtin_fma(x.im, g.re, Ya[c2][js].im));
+                  cfma(Ya[c2][js], X[row][q][js], G[row * M + js * 64]);
                 }
               }
             }
@@ -432,20 +404,7 @@ pbs_small_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_id
         if (!SMD_NOINV) fft512_inv_tw(V, xch, T, lane, gi2, 0);
       }
 #pragma unroll
-      for (int m = 0; m < 8; ++m) {
-        const double tr = V[m].re + RND_MAGIC, ti = V[m].im + RND_MAGIC;
-        if constexpr (RESID) {
-          max_resid = fmax(max_resid, fabs(V[m].re - (tr - RND_MAGIC)));
-          max_resid = fmax(max_resid, fabs(V[m].im - (ti - RND_MAGIC)));
-        }
-        if constexpr (li == 0) {
-          A[m] += (uint64_t)__double_as_longlong(tr) - limb_magic_all(SM_LIMBS, SM_SUB_BITS);
-          A[m + 8] += (uint64_t)__double_as_longlong(ti) - limb_magic_all(SM_LIMBS, SM_SUB_BITS);
-        } else {
-          A[m] += (uint64_t)__double_as_longlong(tr) << (16 * li);
-          A[m + 8] += (uint64_t)__double_as_longlong(ti) << (16 * li);
-        }
-      }
+      for (int m = 0; m < 8; ++m) grid_recombine_one<16, SM_LIMBS, RESID>(li, A[m], A[m + 8], V[m], max_resid);
 #pragma unroll
       for (int m = 0; m < 16; ++m) pin(A[m]);
       if constexpr (RESID) pin(max_resid);
@@ -474,14 +433,12 @@ pbs_small_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_id
   if constexpr (RESID) report_resid(max_resid, lane, active, resid_out);
 }
 
-template <int N, int K1, int SUBS, int NQ, bool RESID>
-static int launch_small_t(const PbsArgs& a) {
-  return launch_fused(pbs_small_kernel<N, K1, SUBS, NQ, RESID>, SM_CTS, SM_CTS * 128, pbs_small_lds_bytes(N, K1), a);
-}
-
 template <int N, int K1, int SUBS, int NQ>
 static int launch_small_r(const PbsArgs& a) {
-  return a.resid ? launch_small_t<N, K1, SUBS, NQ, true>(a) : launch_small_t<N, K1, SUBS, NQ, false>(a);
+  return with_resid(a, [&](auto R) {
+    return launch_fused(pbs_small_kernel<N, K1, SUBS, NQ, decltype(R)::value>, SM_CTS, SM_CTS * 128,
+                        pbs_small_lds_bytes(N, K1), a);
+  });
 }
 
 template <int N, int K1>
@@ -494,11 +451,7 @@ static int launch_small_n(const PbsArgs& a) {
 
 int pbs_small_launch(const PbsArgs& a) {
   if (a.N == 512 && a.k == 4) return pbs512k4_launch(a);  // five polynomials: four waves (pbs512k4.hip)
-  if (!(a.limbs == (uint32_t)SM_LIMBS && pbs_small_ok(a.k, a.N, a.level, a.base_log))) {
-    set_error("unsupported PBS parameters: N=%u k=%u level=%u base_log=%u limbs=%u", a.N, a.k, a.level, a.base_log,
-              a.limbs);
-    return -2;
-  }
+  if (!(a.limbs == (uint32_t)SM_LIMBS && pbs_small_ok(a.k, a.N, a.level, a.base_log))) return reject_params(a);
   if (a.num_samples == 0) return 0;
   if (a.N == 512) return launch_small_n<512, 4>(a);
   return a.k == 5 ? launch_small_n<256, 6>(a) : launch_small_n<256, 7>(a);
