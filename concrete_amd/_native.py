@@ -45,6 +45,17 @@ SIGNATURES = {
                                         u32, vp, u64]),
     "concrete_hip_extract_bits_scratch_bytes": (u64, [u32, u32, u32, u32, u32, u32]),
     "concrete_hip_extract_bits_supported": (i32, [u32, u32, u32, u32, u32, u32, u32, u32]),
+    "scratch_cuda_cmux_tree_64": (None, [vp, u32, C.POINTER(vp), u32, u32, u32, u32, u32, u32, C.c_bool]),
+    "cuda_cmux_tree_64": (None, [vp, u32, vp, vp, vp, vp, u32, u32, u32, u32, u32, u32, u32]),
+    "cleanup_cuda_cmux_tree": (None, [vp, u32, C.POINTER(vp)]),
+    "scratch_cuda_blind_rotation_sample_extraction_64": (None, [vp, u32, C.POINTER(vp), u32, u32, u32, u32, u32, u32,
+                                                                C.c_bool]),
+    "cuda_blind_rotate_and_sample_extraction_64": (None, [vp, u32, vp, vp, vp, vp, u32, u32, u32, u32, u32, u32, u32]),
+    "cleanup_cuda_blind_rotation_sample_extraction": (None, [vp, u32, C.POINTER(vp)]),
+    "concrete_hip_vertical_packing": (i32, [vp, u32, vp, vp, vp, vp, u32, u32, u32, u32, u32, u32, u32, u32, vp, u64,
+                                            vp, C.POINTER(C.c_double)]),
+    "concrete_hip_vertical_packing_scratch_bytes": (u64, [u32, u32, u32, u32, u32, u32, u32]),
+    "concrete_hip_vertical_packing_supported": (i32, [u32, u32, u32, u32]),
     "concrete_hip_abi_version": (u32, []),
     "concrete_hip_last_error": (C.c_char_p, []),
     "concrete_hip_pbs_supported": (i32, [u32, u32, u32, u32]),

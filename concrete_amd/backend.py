@@ -384,3 +384,43 @@ def crt_extract_bits(p: PbsParams, fbsk, ksk_dev, blocks, moduli):
     out = extract_bits(p, fbsk, ksk_dev, shifted, np.tile(nbs, batch), np.tile([64 - nb for nb in nbs], batch),
                        out_row_offsets=offs)
     return out.reshape(batch, per_value, p.n + 1)
+
+
+# ---------------------------------------------------------------------------------------
+# WoP-PBS stage 3: vertical packing (concrete_hip_vertical_packing)
+# ---------------------------------------------------------------------------------------
+def vertical_packing_supported(p: PbsParams) -> bool:
+    return bool(_native.lib().concrete_hip_vertical_packing_supported(p.k, p.N, p.level, p.base_log))
+
+
+def vertical_packing_scratch_bytes(p: PbsParams, r: int, mbr_size: int, tau: int, num_lookups: int = 1) -> int:
+    return int(_native.lib().concrete_hip_vertical_packing_scratch_bytes(p.k, p.N, p.level, r, mbr_size, tau,
+                                                                         num_lookups))
+
+
+def vertical_packing(p: PbsParams, ggsw, luts, r: int, mbr_size: int, num_lookups: int = 1, out=None, tree_out=None,
+                     scratch=None, resid=None, want_tree: bool = False):
+    """Vertical packing on device tensors.  ggsw: (num_lookups, r + mbr_size, level, k+1, k+1, N) standard
+    GGSWs, the tree's first, most significant bit first (None when r + mbr_size == 0); luts: (tau, 2^r, N),
+    shared by the lookups.  Returns (lwe, tree, max|G|): lwe (num_lookups, tau, kN+1) int64; tree
+    (num_lookups, tau, (k+1)N), the CMUX tree's result, when tree_out is given or want_tree is set, else None;
+    max|G| the measured spectrum magnitude of the converted GGSWs.  p.n is not used."""
+    torch = _torch()
+    device = luts.device
+    tau = luts.shape[0]
+    if luts.shape[1] != 1 << r or luts.shape[2] != p.N or not luts.is_contiguous():
+        raise ValueError(f"luts: need a contiguous ({tau}, {1 << r}, {p.N}) tensor, got {tuple(luts.shape)}")
+    words = num_lookups * (r + mbr_size) * p.level * (p.k + 1) ** 2 * p.N
+    if words and (ggsw is None or ggsw.numel() != words or not ggsw.is_contiguous()):
+        raise ValueError(f"ggsw: need {words} contiguous words for {num_lookups} x {r + mbr_size} GGSWs")
+    if out is None:
+        out = torch.empty((num_lookups, tau, p.lwe_out_size), dtype=torch.int64, device=device)
+    if tree_out is None and want_tree:
+        tree_out = torch.empty((num_lookups, tau, p.glwe_size), dtype=torch.int64, device=device)
+    max_g = C.c_double(0.0)
+    _native.check(_native.lib().concrete_hip_vertical_packing(
+        _stream(device), _gpu_index(device), _ptr(out), _ptr(tree_out), _ptr(ggsw) if words else None, _ptr(luts),
+        p.k, p.N, p.base_log, p.level, r, mbr_size, tau, num_lookups, _ptr(scratch),
+        0 if scratch is None else scratch.numel() * scratch.element_size(), _ptr(resid), C.byref(max_g)),
+        "concrete_hip_vertical_packing")
+    return out, tree_out, max_g.value

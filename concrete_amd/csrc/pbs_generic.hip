@@ -39,6 +39,7 @@
 #include "keycheck.hpp"
 #include "pbs.hpp"
 #include "companion.hpp"
+#include "vertical_packing.hpp"
 
 // Streaming (non-temporal) accesses of the per-call spectra and accumulators, which cross HBM once
 // per CMUX step and are not re-read from L2 (round 6, A/B in DESIGN.md §4.5): GEN_NT_STORES 2 = every
@@ -2646,6 +2647,139 @@ __global__ void __launch_bounds__(Geo<M>::THREADS) gen_convert_kernel(cplx* G, c
 }
 
 // ------------------------------------------------------------------------------------------
+// vertical packing (vertical_packing.hip): dst = c0 + G [x] (c1 - c0) on GGSWs that
+// differ per lookup.  One workgroup (the TH threads of one polynomial) does output column c of one
+// CMUX on chip: per digit row (r, q, t) of c1 - c0 one forward transform in LDS, its products with
+// the key's limbs into the L slot accumulators Y_m (registers; L <= CMUX_MAX_LIMBS), then L inverse
+// transforms, round_acc and c0.  No spectrum goes to memory.  The k + 1 columns of a CMUX repeat the
+// forward transforms; every CMUX of a launch within a lookup reads the same GGSW, from L2 after the
+// first.  Key in natural frequency order for every N (vp_convert_launch).
+// ------------------------------------------------------------------------------------------
+struct CmuxKernelArgs {
+  uint64_t* dst;        // [count][K1][N]
+  const uint64_t* src;  // CMUX_PAIR: nodes 2x, 2x + 1; CMUX_ROTATE: node x; CMUX_LEAF: LUT polynomials [2 per_lookup][N]
+  const cplx* G;        // [lookups][key_stride] GGSWs, each [K1 c][L lim][K1 r][l q][M]
+  const cplx* Wfull;
+  const cplx* Z;
+  unsigned long long* resid;
+  uint32_t k, level, base_log, bits, limbs, subs;
+  uint32_t per_lookup, key_stride, key_index, rot;
+};
+enum { CMUX_LEAF, CMUX_PAIR, CMUX_ROTATE };
+constexpr int CMUX_MAX_LIMBS = 6;  // every format of k <= 3, N <= 2048 (generic_key_format)
+// complex values per thread and transform: 4 (radix-4 passes, M / 4 threads) keeps the L x VPT accumulators and
+// the rest under 256 VGPRs, two waves per SIMD; 8 (the step kernel's radix-8 geometry) needs 388 at M = 1024
+constexpr int CMUX_VPT = 4;
+
+template <int M, int MODE>
+__global__ void __launch_bounds__(M / CMUX_VPT) gen_cmux_kernel(CmuxKernelArgs a) {
+  constexpr int N = 2 * M, VPT = CMUX_VPT, TH = M / VPT, LC = CMUX_MAX_LIMBS;
+  constexpr int TWN = tile_tw_entries<M, TH>();
+  __shared__ cplx lds[M + TWN + M];
+  cplx* buf = lds;
+  cplx* W = lds + M;
+  cplx* Zl = W + TWN;
+  const int tid = threadIdx.x;
+  build_tile_tw<M, TH>(W, a.Wfull, tid, TH);
+  for (int e = tid; e < M; e += TH) Zl[e] = a.Z[e];
+  __syncthreads();
+  const uint32_t K1 = a.k + 1, L = a.limbs;
+  const uint32_t x = blockIdx.x / K1, c = blockIdx.x % K1;  // CMUX of the launch, output column
+  const uint64_t lim_stride = (uint64_t)K1 * a.level * M;   // one key limb: [K1 r][l q][M]
+  const cplx* Gc = a.G + (((uint64_t)(x / a.per_lookup) * a.key_stride + a.key_index) * K1 + c) * L * lim_stride;
+  // c0 (and c1) of this CMUX: GLWEs, or at the leaves the two LUT polynomials (bodies of trivial GLWEs)
+  const uint64_t* c0 = MODE == CMUX_LEAF   ? a.src + (uint64_t)(x % a.per_lookup) * 2 * N
+                       : MODE == CMUX_PAIR ? a.src + (uint64_t)x * 2 * K1 * N
+                                           : a.src + (uint64_t)x * K1 * N;
+  const uint64_t* c1 = MODE == CMUX_LEAF ? c0 + N : c0 + (uint64_t)K1 * N;  // unused by CMUX_ROTATE
+  // this thread's coefficients: j = tid + e TH (e < VPT) and j + M (element e + VPT)
+  auto coef = [&](int e) { return (uint32_t)(tid + (e % VPT) * TH + (e / VPT) * M); };
+
+  cplx Y[LC][VPT];
+#pragma unroll
+  for (int m = 0; m < LC; ++m)
+#pragma unroll
+    for (int e = 0; e < VPT; ++e) Y[m][e] = {0.0, 0.0};
+  const int nrep = 64 - (int)(a.level * a.base_log), logB = (int)a.base_log;
+  const SubDigit<uint64_t, true> sub(a.bits, a.subs > 1);
+  // the mask rows of a leaf's c1 - c0 are exact zeros: their digits are skipped
+#pragma unroll 1
+  for (uint32_t r = MODE == CMUX_LEAF ? a.k : 0u; r < K1; ++r) {
+    uint64_t St[2 * VPT];  // decomposer state of row r of c1 - c0
+#pragma unroll
+    for (int e = 0; e < 2 * VPT; ++e) {
+      const uint32_t j = coef(e);
+      uint64_t d;
+      if constexpr (MODE == CMUX_LEAF) d = c1[j] - c0[j];
+      else if constexpr (MODE == CMUX_PAIR) d = c1[(uint64_t)r * N + j] - c0[(uint64_t)r * N + j];
+      else d = neg_at<N>(c0 + (uint64_t)r * N, j + a.rot) - c0[(uint64_t)r * N + j];
+      St[e] = nrep > 0 ? decomp_init(d, nrep) : d;
+    }
+#pragma unroll 1
+    for (uint32_t q = 0; q < a.level; ++q) {
+      int64_t D[2 * VPT];
+#pragma unroll
+      for (int e = 0; e < 2 * VPT; ++e) D[e] = decomp_next<uint64_t>(St[e], logB);
+#pragma unroll 1
+      for (uint32_t t = 0; t < a.subs; ++t) {
+#pragma unroll
+        for (int e = 0; e < VPT; ++e) {
+          const int64_t s0 = sub.take(D[e]), s1 = sub.take(D[e + VPT]);
+          const int j = tid + e * TH;
+          buf[sw(j)] = cmul(cplx{(double)s0, (double)s1}, Zl[j]);
+        }
+        lds_sync<TH>();
+        tile_fft<M, TH, false>(buf, W, tid);
+        // slot m takes sub-digit t times key limb m - t (slots >= L vanish mod 2^64)
+        const cplx* Gr = Gc + ((uint64_t)r * a.level + q) * M + tid;
+#pragma unroll
+        for (int m = 0; m < LC; ++m) {
+          if ((uint32_t)m < L && (uint32_t)m >= t) {
+            const cplx* Gm = Gr + (uint64_t)(m - t) * lim_stride;
+#pragma unroll
+            for (int e = 0; e < VPT; ++e) {
+              const cplx s = buf[sw(tid + e * TH)], g = Gm[e * TH];
+              Y[m][e].re = __builtin_fma(s.re, g.re, __builtin_fma(-s.im, g.im, Y[m][e].re));
+              Y[m][e].im = __builtin_fma(s.re, g.im, __builtin_fma(s.im, g.re, Y[m][e].im));
+            }
+          }
+        }
+        lds_sync<TH>();
+      }
+    }
+  }
+
+  // dst_c = c0_c + sum_m 2^{m b} round(iFFT(Y_m) conj(zeta^j)); the key spectra carry the 1/M
+  uint64_t A[2 * VPT];
+#pragma unroll
+  for (int e = 0; e < 2 * VPT; ++e) {
+    if constexpr (MODE == CMUX_LEAF) A[e] = c == a.k ? c0[coef(e)] : 0ull;
+    else A[e] = c0[(uint64_t)c * N + coef(e)];
+  }
+  double max_resid = 0.0;
+#pragma unroll
+  for (int m = 0; m < LC; ++m) {
+    if ((uint32_t)m < L) {
+#pragma unroll
+      for (int e = 0; e < VPT; ++e) buf[sw(tid + e * TH)] = Y[m][e];
+      lds_sync<TH>();
+      tile_fft<M, TH, true>(buf, W, tid);
+      const uint32_t sh = m * a.bits;
+#pragma unroll
+      for (int e = 0; e < VPT; ++e) {
+        const int j = tid + e * TH;
+        round_acc(cmulc(buf[sw(j)], Zl[j]), sh, A[e], A[e + VPT], max_resid);
+      }
+      lds_sync<TH>();
+    }
+  }
+  uint64_t* out = a.dst + ((uint64_t)x * K1 + c) * N;
+#pragma unroll
+  for (int e = 0; e < 2 * VPT; ++e) out[coef(e)] = A[e];
+  if (a.resid) report_resid(max_resid, tid & 63, true, a.resid);
+}
+
+// ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
 struct Tables {
@@ -3133,6 +3267,80 @@ int convert_bsk_generic_launch(const ConvertArgs& a) {
   }
 #undef GEN_CONV
   return launch_ok("convert");
+}
+
+// ------------------------------------------------------------------------------------------
+// vertical packing launches (vertical_packing.hpp)
+// ------------------------------------------------------------------------------------------
+bool vp_params_ok(uint32_t k, uint32_t N, uint32_t level, uint32_t base_log) {
+  if (k > 3 || (N != 512 && N != 1024 && N != 2048) || !generic_pbs_ok(k, N, level, base_log)) return false;
+  return generic_key_format(k, N, level).limbs <= (uint32_t)gen::CMUX_MAX_LIMBS;
+}
+
+int vp_convert_launch(hipStream_t s, void* dest, const uint64_t* src_dev, uint64_t ggsws, uint32_t k, uint32_t N,
+                      uint32_t level, unsigned long long* smax) {
+  using namespace gen;
+  const KeyFormat fmt = generic_key_format(k, N, level);
+  const uint64_t blocks = ggsws * level * (k + 1) * (k + 1);
+  if (fmt.kind != KeyKind::GENERIC || blocks >> 31) {
+    set_error("GGSW conversion: unsupported k=%u N=%u level=%u, or too many GGSWs", k, N, level);
+    return -2;
+  }
+  if (blocks == 0) return 0;
+  const Tables tb = tables_for(N);
+#define VP_CONV(MM)                                                                                            \
+  hipLaunchKernelGGL(gen_convert_kernel<MM>, dim3((uint32_t)blocks), dim3(Geo<MM>::THREADS), 0, s,              \
+                     reinterpret_cast<cplx*>(dest), src_dev, tb.Wfull, tb.Wlo, tb.Whi, tb.Z, k, level, fmt.bits, \
+                     fmt.limbs, 0u, smax)
+  switch (N) {
+    case 512: VP_CONV(256); break;
+    case 1024: VP_CONV(512); break;
+    case 2048: VP_CONV(1024); break;
+    default: set_error("GGSW conversion: N=%u", N); return -2;
+  }
+#undef VP_CONV
+  return launch_ok("GGSW convert");
+}
+
+template <int M>
+static void launch_cmux(CmuxMode mode, const gen::CmuxKernelArgs& c, uint32_t blocks, hipStream_t st) {
+  using namespace gen;
+  const dim3 g(blocks), b(M / CMUX_VPT);
+  switch (mode) {
+    case CmuxMode::LEAF: hipLaunchKernelGGL((gen_cmux_kernel<M, CMUX_LEAF>), g, b, 0, st, c); break;
+    case CmuxMode::PAIR: hipLaunchKernelGGL((gen_cmux_kernel<M, CMUX_PAIR>), g, b, 0, st, c); break;
+    case CmuxMode::ROTATE: hipLaunchKernelGGL((gen_cmux_kernel<M, CMUX_ROTATE>), g, b, 0, st, c); break;
+  }
+}
+
+int vp_cmux_launch(CmuxMode mode, const CmuxArgs& a) {
+  using namespace gen;
+  if (a.count == 0) return 0;
+  const uint64_t blocks = (uint64_t)a.count * (a.k + 1);
+  if (!vp_params_ok(a.k, a.N, a.level, a.base_log) || blocks >> 31 || a.per_lookup == 0) {
+    set_error("cmux: k=%u N=%u level=%u base_log=%u count=%u outside the kernel's range", a.k, a.N, a.level,
+              a.base_log, a.count);
+    return -2;
+  }
+  const KeyFormat fmt = generic_key_format(a.k, a.N, a.level);
+  const Tables tb = tables_for(a.N);
+  const CmuxKernelArgs c{a.dst,   a.src,      reinterpret_cast<const cplx*>(a.keys),        tb.Wfull,     tb.Z,
+                         a.resid, a.k,        a.level,      a.base_log,   fmt.bits,     fmt.limbs,
+                         (a.base_log + fmt.bits - 1) / fmt.bits, a.per_lookup, a.key_stride, a.key_index, a.rot};
+  switch (a.N) {
+    case 512: launch_cmux<256>(mode, c, (uint32_t)blocks, a.stream); break;
+    case 1024: launch_cmux<512>(mode, c, (uint32_t)blocks, a.stream); break;
+    default: launch_cmux<1024>(mode, c, (uint32_t)blocks, a.stream); break;
+  }
+  return launch_ok("cmux");
+}
+
+int vp_extract_launch(hipStream_t s, uint64_t* out, const uint64_t* glwes, uint32_t count, uint32_t k, uint32_t N) {
+  const uint64_t total = ((uint64_t)k * N + 1) * count;
+  const uint32_t blocks = (uint32_t)std::min<uint64_t>((total + 255) / 256, 256ull * 64);
+  hipLaunchKernelGGL(gen::gen_extract_kernel, dim3(blocks), dim3(256), 0, s, out, (const uint64_t*)nullptr, glwes, 0u,
+                     count, k, N, 0u);
+  return gen::launch_ok("extract");
 }
 
 }  // namespace chip

@@ -125,6 +125,36 @@ void cuda_extract_bits_64(void *stream, uint32_t gpu_index, void *list_lwe_array
                           uint32_t level_count_ksk, uint32_t number_of_samples, uint32_t max_shared_memory);
 void cleanup_cuda_extract_bits(void *stream, uint32_t gpu_index, int8_t **bit_extract_buffer);
 
+/* Vertical packing, stage 3 of the WoP-PBS (concrete-cuda rust_api/src/cuda_bind.rs:369-488; DESIGN.md
+ * §4.19).  ggsw_in: standard-domain GGSWs of level_count x (k+1) x (k+1) x N words each, level matrix 0
+ * being decomposition level 1 (one entry of a standard bootstrapping key).
+ * cuda_cmux_tree_64: `r` GGSWs, most significant bit first, select one of 2^r LUT polynomials per output;
+ * lut_vector is [tau][2^r][N], glwe_array_out [tau][(k+1)N].
+ * cuda_blind_rotate_and_sample_extraction_64: lut_vector holds `tau` GLWEs of (k+1)N words (what the tree
+ * call wrote); GGSW j (j = mbr_size-1 down to 0) turns acc into X^(-2^(mbr_size-1-j)) acc when its bit is
+ * set; lwe_out receives tau rows of kN + 1 words.
+ * max_shared_memory is accepted and ignored.  A scratch call with allocate_gpu_memory = false leaves NULL,
+ * and a NULL buffer makes the call take stream-ordered pool scratch.  Each call converts its GGSWs and reads
+ * their largest spectrum back before it computes: ONE host synchronisation of the stream per call.  Bad
+ * arguments, unsupported parameters and GGSWs that fail the exactness gate abort. */
+void scratch_cuda_cmux_tree_64(void *stream, uint32_t gpu_index, int8_t **cmux_tree_buffer, uint32_t glwe_dimension,
+                               uint32_t polynomial_size, uint32_t level_count, uint32_t r, uint32_t tau,
+                               uint32_t max_shared_memory, bool allocate_gpu_memory);
+void cuda_cmux_tree_64(void *stream, uint32_t gpu_index, void *glwe_array_out, const void *ggsw_in,
+                       const void *lut_vector, int8_t *cmux_tree_buffer, uint32_t glwe_dimension,
+                       uint32_t polynomial_size, uint32_t base_log, uint32_t level_count, uint32_t r, uint32_t tau,
+                       uint32_t max_shared_memory);
+void cleanup_cuda_cmux_tree(void *stream, uint32_t gpu_index, int8_t **cmux_tree_buffer);
+void scratch_cuda_blind_rotation_sample_extraction_64(void *stream, uint32_t gpu_index, int8_t **br_se_buffer,
+                                                      uint32_t glwe_dimension, uint32_t polynomial_size,
+                                                      uint32_t level_count, uint32_t mbr_size, uint32_t tau,
+                                                      uint32_t max_shared_memory, bool allocate_gpu_memory);
+void cuda_blind_rotate_and_sample_extraction_64(void *stream, uint32_t gpu_index, void *lwe_out, const void *ggsw_in,
+                                                const void *lut_vector, int8_t *br_se_buffer, uint32_t mbr_size,
+                                                uint32_t tau, uint32_t glwe_dimension, uint32_t polynomial_size,
+                                                uint32_t base_log, uint32_t level_count, uint32_t max_shared_memory);
+void cleanup_cuda_blind_rotation_sample_extraction(void *stream, uint32_t gpu_index, int8_t **br_se_buffer);
+
 /* ------------------------------------------------------------------------------------------
  * Part 2: extensions (return 0 on success, < 0 on error; message via concrete_hip_last_error)
  * ------------------------------------------------------------------------------------------ */
@@ -137,7 +167,9 @@ void cleanup_cuda_extract_bits(void *stream, uint32_t gpu_index, int8_t **bit_ex
  *    concrete_hip_set_status_slot_cap), converted keys checked against the certified bound
  *    (concrete_hip_key_spectrum_max)).
  * Bit extraction (cuda_extract_bits_64, concrete_hip_extract_bits*) was added without a new version:
- * the value stays 5, and a caller finds the capability through concrete_hip_extract_bits_supported. */
+ * the value stays 5, and a caller finds the capability through concrete_hip_extract_bits_supported.
+ * The same holds for vertical packing (cuda_cmux_tree_64, cuda_blind_rotate_and_sample_extraction_64,
+ * concrete_hip_vertical_packing*): concrete_hip_vertical_packing_supported. */
 uint32_t concrete_hip_abi_version(void);
 /* thread-local message of the last failed concrete_hip_* call */
 const char *concrete_hip_last_error(void);
@@ -246,6 +278,47 @@ uint64_t concrete_hip_extract_bits_scratch_bytes(uint32_t lwe_dimension_in, uint
 int concrete_hip_extract_bits_supported(uint32_t lwe_dimension_in, uint32_t lwe_dimension_out,
                                         uint32_t glwe_dimension, uint32_t polynomial_size, uint32_t base_log_bsk,
                                         uint32_t level_count_bsk, uint32_t base_log_ksk, uint32_t level_count_ksk);
+/* Vertical packing with a status code, batched over num_lookups independent lookups that share the LUTs
+ * (DESIGN.md §4.19).  Per lookup: a CMUX tree over the first r GGSWs (most significant bit first) picks one
+ * of the 2^r LUT polynomials of each of the tau outputs; the next mbr_size GGSWs rotate the result, GGSW j
+ * (j = mbr_size-1 down to 0) by X^(-2^(mbr_size-1-j)); the sample extraction of the result is written to
+ * lwe_array_out.  cmux(c0, c1, G) = c0 + G [x] (c1 - c0) with the exact external product: the u64 result is
+ * the integer definition's, bit for bit.  Every pointer but ggsw_spectrum_max is device memory.
+ *   lwe_array_out  [num_lookups][tau][kN+1]; may be NULL only when mbr_size == 0 and glwe_tree_out is given
+ *   glwe_tree_out  optional [num_lookups][tau][(k+1)N]: the tree's result
+ *   ggsw_in        [num_lookups][r + mbr_size] standard-domain GGSWs of level x (k+1) x (k+1) x N words,
+ *                  the tree's first (may be NULL when r + mbr_size == 0)
+ *   lut_vector     [tau][2^r][N]
+ *   scratch        16-byte aligned, at least concrete_hip_vertical_packing_scratch_bytes() bytes, or NULL
+ *                  for stream-ordered pool scratch
+ *   resid_bits     optional device u64, as concrete_hip_pbs
+ *   ggsw_spectrum_max  optional HOST double: the measured max|G| of the converted GGSWs (0 without GGSWs);
+ *                  also written when the gate refuses the call, left untouched by every other refusal
+ * The GGSWs are converted into the general key format and gated like any converted key: the call reads
+ * their largest limb-spectrum magnitude back (ONE host synchronisation of the stream per call) and returns -2
+ * when the general format's certified rounding bound (the bound of the general key format of
+ * (k, N, level), whatever the primary format of that shape) at that magnitude and base_log reaches 1/2.  That
+ * is concrete_hip_generic_error_bound's value where that function answers; it answers -1 for a (k, N, level)
+ * whose primary format is a hand-tuned kernel's, e.g. (1, 1024, 3) and (1, 2048, 2), and the gate applies
+ * there all the same.  After that the call is stream-ordered: no host synchronisation, device-to-host copy
+ * or allocation between the layers.
+ * Checked before the first device call: -1 null lut_vector, or null ggsw_in with r + mbr_size > 0;
+ * -3 tau == 0, num_lookups == 0, r > 24, mbr_size > log2 N, sizes that overflow, lwe_array_out == NULL with
+ * mbr_size > 0 or without glwe_tree_out, a scratch buffer too small or misaligned; -2 parameters for which
+ * concrete_hip_vertical_packing_supported is 0.  Nothing is written by a refused call. */
+int concrete_hip_vertical_packing(void *stream, uint32_t gpu_index, uint64_t *lwe_array_out, uint64_t *glwe_tree_out,
+                                  const uint64_t *ggsw_in, const uint64_t *lut_vector, uint32_t glwe_dimension,
+                                  uint32_t polynomial_size, uint32_t base_log, uint32_t level_count, uint32_t r,
+                                  uint32_t mbr_size, uint32_t tau, uint32_t num_lookups, void *scratch,
+                                  uint64_t scratch_bytes, uint64_t *resid_bits, double *ggsw_spectrum_max);
+/* scratch bytes of such a call; 0 for tau == 0, num_lookups == 0, r > 24, mbr_size > log2 N, a (k, N, level)
+ * without a general key format, or sizes that overflow.  Does not decrease with r, tau or num_lookups. */
+uint64_t concrete_hip_vertical_packing_scratch_bytes(uint32_t glwe_dimension, uint32_t polynomial_size,
+                                                     uint32_t level_count, uint32_t r, uint32_t mbr_size, uint32_t tau,
+                                                     uint32_t num_lookups);
+/* 1 for N = 512, 1024, 2048, k <= 3 and a (level, base_log) the general path keeps exact, else 0 */
+int concrete_hip_vertical_packing_supported(uint32_t glwe_dimension, uint32_t polynomial_size, uint32_t level_count,
+                                            uint32_t base_log);
 /* Fourier key registered for a `dest` of cuda_convert_lwe_programmable_bootstrap_key_64, or NULL */
 const void *concrete_hip_lookup_bsk(const void *bootstrapping_key);
 /* Release what the backend derived from device buffer `ptr` (a registered Fourier key whose `dest`
