@@ -44,16 +44,36 @@ __host__ __device__ constexpr uint32_t ks_ichunk(uint32_t level) {
 // 1 = always when exact; A/B and test switch)
 constexpr uint32_t KS_MFMA_MIN_BATCH = 64;
 
+// The rows of a batch of ciphertexts: sample smp is row idx[smp] of `base` when the call gave an
+// index array, row smp otherwise.
+template <typename T>
+struct Rows {
+  T* base;
+  const uint64_t* idx;
+  uint32_t width;  // words per row
+  __device__ __forceinline__ uint64_t offset(uint32_t smp) const { return (idx ? idx[smp] : smp) * (uint64_t)width; }
+  __device__ __forceinline__ T* row(uint32_t smp) const { return base + offset(smp); }
+  __device__ __forceinline__ T& at(uint32_t smp, uint32_t j) const { return base[offset(smp) + j]; }  // word j of the row
+};
+
 // Split-K (SPLIT): blockIdx.y takes mask positions [i_begin, i_end) and adds its partial sums
 // into pre-zeroed outputs with 64-bit atomics (wrapping addition is exact and order-free, so
 // the result is bit-identical); split 0 adds the body.  Used when the batch alone gives too
 // few workgroups for the chip (large n_in, small batches).
 __global__ void keyswitch_zero_kernel(uint64_t* out, const uint64_t* out_idx, uint32_t W, uint32_t num_samples) {
+  const Rows<uint64_t> rout{out, out_idx, W};
   const uint64_t total = (uint64_t)W * num_samples;
   for (uint64_t g = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; g < total; g += (uint64_t)gridDim.x * blockDim.x) {
     const uint32_t smp = (uint32_t)(g / W), j = (uint32_t)(g % W);
-    out[(out_idx ? out_idx[smp] : smp) * (uint64_t)W + j] = 0ull;
+    rout.at(smp, j) = 0ull;
   }
+}
+
+// Bit offset of key chunk c of NCH (3: 22/21/21 bits, 4: 16 bits each; chunk NCH would start at bit
+// 64): where the key word is split and where the chunk's int32 sum goes back into the u64 sum.
+template <int NCH>
+__host__ __device__ constexpr int chunk_shift(int c) {
+  return NCH == 3 ? (c == 0 ? 0 : c == 1 ? 22 : c == 2 ? 43 : 64) : 16 * c;
 }
 
 // NCH > 0: the 64-bit products d * k split into NCH key chunks (3: 22/21/21 bits, 4: 16 bits
@@ -82,6 +102,8 @@ keyswitch_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_id
 #pragma unroll
     for (int u = 0; u < U; ++u) acc[s][u] = 0ull;
   const int nrep = 64 - (int)(level * base_log);
+  const Rows<const uint64_t> rin{in, in_idx, n_in + 1};
+  const Rows<uint64_t> rout{out, out_idx, W};
 
   const uint32_t i_begin = SPLIT ? blockIdx.y * i_per_split : 0u;
   const uint32_t i_end = SPLIT ? min(n_in, i_begin + i_per_split) : n_in;
@@ -91,7 +113,7 @@ keyswitch_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_id
       const uint32_t s = e / ich, ii = e % ich;
       const uint32_t smp = s0 + s, i = i0 + ii;
       uint64_t a = 0ull;
-      if (smp < num_samples && i < i_end) a = in[(in_idx ? in_idx[smp] : smp) * (uint64_t)(n_in + 1) + i];
+      if (smp < num_samples && i < i_end) a = rin.at(smp, i);
       uint64_t st = decomp_init(a, nrep);
       for (uint32_t t = 0; t < level; ++t) dig[ii * level + t][s] = (dig_t)decomp_next64(st, (int)base_log);
     }
@@ -116,14 +138,10 @@ keyswitch_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_id
               const uint32_t j = jz + tid + u * KS_THREADS;
               const uint64_t kv = j < W ? row[j] : 0ull;
               int32_t kc[NCH];
-              if constexpr (NCH == 3) {
-                kc[0] = (int32_t)(kv & 0x3fffffu);
-                kc[1] = (int32_t)((kv >> 22) & 0x1fffffu);
-                kc[2] = (int32_t)(kv >> 43);
-              } else {
 #pragma unroll
-                for (int c = 0; c < NCH; ++c) kc[c] = (int32_t)((kv >> (16 * c)) & 0xffffu);
-              }
+              for (int c = 0; c < NCH; ++c)  // chunk c: bits chunk_shift(c) .. chunk_shift(c + 1) - 1
+                kc[c] = (int32_t)((kv >> chunk_shift<NCH>(c)) &
+                                  ((1ull << (chunk_shift<NCH>(c + 1) - chunk_shift<NCH>(c))) - 1));
 #pragma unroll
               for (int s = 0; s < KS_TILE; ++s) {
                 const int32_t d = dig[ii * level + t][s];
@@ -139,8 +157,7 @@ keyswitch_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_id
           for (int u = 0; u < U; ++u) {
             uint64_t sum = 0ull;
 #pragma unroll
-            for (int c = 0; c < NCH; ++c)
-              sum += (uint64_t)(int64_t)ca[s][u][c] << (NCH == 3 ? (c == 0 ? 0 : c == 1 ? 22 : 43) : 16 * c);
+            for (int c = 0; c < NCH; ++c) sum += (uint64_t)(int64_t)ca[s][u][c] << chunk_shift<NCH>(c);
             acc[s][u] -= sum;
           }
       }
@@ -163,8 +180,8 @@ keyswitch_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_id
   for (int s = 0; s < KS_TILE; ++s) {
     const uint32_t smp = s0 + s;
     if (smp >= num_samples) break;
-    const uint64_t* ci = in + (in_idx ? in_idx[smp] : smp) * (uint64_t)(n_in + 1);
-    uint64_t* co = out + (out_idx ? out_idx[smp] : smp) * (uint64_t)W;
+    const uint64_t* ci = rin.row(smp);
+    uint64_t* co = rout.row(smp);
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const uint32_t j = jz + tid + u * KS_THREADS;
@@ -190,9 +207,9 @@ keyswitch_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_id
 // ------------------------------------------------------------------------------------------
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
-constexpr int KSM_ROWS = 128;  // rows (samples) per 4-wave workgroup
-constexpr int KSM_COLS = 64;   // columns (output words) per 4-wave workgroup
-constexpr int KSM_KB = 64;     // K per register block (Kp is padded to a multiple of it)
+// tile of one workgroup: rows (samples) x columns (output words), K in blocks of KSL_KB (Kp is padded
+// to a multiple of it), brought through an LDS ring of KSL_RS stages
+constexpr int KSL_ROWS = 128, KSL_COLS = 64, KSL_KB = 64, KSL_RS = 3;
 
 __global__ void __launch_bounds__(256) ks_digits_i8_kernel(int8_t* __restrict__ A, const uint64_t* __restrict__ in,
                                                          const uint64_t* __restrict__ in_idx, uint32_t n_in,
@@ -203,7 +220,7 @@ __global__ void __launch_bounds__(256) ks_digits_i8_kernel(int8_t* __restrict__ 
   const uint32_t b = (uint32_t)(g / ipr), i = (uint32_t)(g % ipr);
   const int nrep = 64 - (int)(level * base_log);
   uint64_t a = 0ull;
-  if (b < num_samples && i < n_in) a = in[(in_idx ? in_idx[b] : b) * (uint64_t)(n_in + 1) + i];
+  if (b < num_samples && i < n_in) a = Rows<const uint64_t>{in, in_idx, n_in + 1}.at(b, i);
   uint64_t st = decomp_init(a, nrep);
   int8_t* row = A + (uint64_t)b * Ks;
   for (uint32_t t = 0; t < level; ++t) {
@@ -237,98 +254,38 @@ __global__ void __launch_bounds__(256) ks_chunks_i8_kernel(int8_t* __restrict__ 
     *reinterpret_cast<uint4*>(Bt + ((uint64_t)c * NP + j) * Ks + k0) = make_uint4(w[c][0], w[c][1], w[c][2], w[c][3]);
 }
 
-// one wave = 64 samples (two 32-row tiles) x 32 output words, all 8 chunks: 16 int32
-// accumulator tiles (256 AGPRs), so each key-chunk fragment it loads serves two MFMAs; 4 waves
-// per workgroup cover 128 x 64.  K in register blocks of KSM_KB = 64: lane half h reads the 32
-// contiguous bytes [32 h, 32 h + 32) of the block for its row / column and feeds bytes
-// 16 s .. 16 s + 15 to step s (any k order is exact as long as A and B use the same one); the
-// next block's 20 fragments are loaded while the current block's 32 MFMAs run.
-__global__ void __launch_bounds__(256) ks_mfma_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_idx,
-                                                    const uint64_t* __restrict__ in, const uint64_t* __restrict__ in_idx,
-                                                    const int8_t* __restrict__ A, const int8_t* __restrict__ Bt,
-                                                    uint32_t n_in, uint32_t n_out, uint32_t num_samples, uint32_t NP,
-                                                    uint32_t Kp, uint32_t Ks, uint32_t k_per_split) {
-  constexpr int RT = 2, SPB = KSM_KB / 32;  // row tiles per wave, MFMA k-steps per block
-  // split-K (gridDim.z > 1): this workgroup sums k in [k_begin, k_end) and adds its partial
-  // result into pre-zeroed outputs with 64-bit atomics (wrapping addition: exact, order-free);
-  // split 0 adds the body
-  const uint32_t k_begin = blockIdx.z * k_per_split, k_end = min(Kp, k_begin + k_per_split);
-  const bool split = gridDim.z > 1;
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const uint32_t row0 = blockIdx.y * KSM_ROWS + 64 * (w >> 1), col0 = blockIdx.x * KSM_COLS + 32 * (w & 1);
-  const int8_t* ap = A + (uint64_t)(row0 + (lane & 31)) * Ks + (KSM_KB / 2) * (lane >> 5);
-  const int8_t* bp = Bt + (uint64_t)(col0 + (lane & 31)) * Ks + (KSM_KB / 2) * (lane >> 5);
-  const uint64_t cstride = (uint64_t)NP * Ks, rstride = 32ull * Ks;
-  v16i acc[RT][8];
-#pragma unroll
-  for (int t = 0; t < RT; ++t)
-#pragma unroll
-    for (int c = 0; c < 8; ++c)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[t][c][r] = 0;
-  v4i av[RT][SPB], bv[8][SPB];
-  auto load_block = [&](uint32_t k0, v4i (&a4)[RT][SPB], v4i (&b4)[8][SPB]) __attribute__((always_inline)) {
-#pragma unroll
-    for (int t = 0; t < RT; ++t)
-#pragma unroll
-      for (int s4 = 0; s4 < SPB; ++s4) a4[t][s4] = *reinterpret_cast<const v4i*>(ap + t * rstride + k0 + 16 * s4);
-#pragma unroll
-    for (int c = 0; c < 8; ++c)
-#pragma unroll
-      for (int s4 = 0; s4 < SPB; ++s4) b4[c][s4] = *reinterpret_cast<const v4i*>(bp + c * cstride + k0 + 16 * s4);
-  };
-  load_block(k_begin, av, bv);
-  for (uint32_t k0 = k_begin; k0 < k_end; k0 += KSM_KB) {
-    v4i an[RT][SPB], bn[8][SPB];
-    const uint32_t kn = k0 + KSM_KB < k_end ? k0 + KSM_KB : k0;  // last block: a harmless reload
-    load_block(kn, an, bn);
-    __builtin_amdgcn_sched_barrier(0);  // all next-block loads issued before this block's MFMAs
-#pragma unroll
-    for (int s4 = 0; s4 < SPB; ++s4)
-#pragma unroll
-      for (int c = 0; c < 8; ++c)
-#pragma unroll
-        for (int t = 0; t < RT; ++t)
-          acc[t][c] = __builtin_amdgcn_mfma_i32_32x32x32_i8(av[t][s4], bv[c][s4], acc[t][c], 0, 0, 0);
-#pragma unroll
-    for (int s4 = 0; s4 < SPB; ++s4) {
-#pragma unroll
-      for (int t = 0; t < RT; ++t) av[t][s4] = an[t][s4];
-#pragma unroll
-      for (int c = 0; c < 8; ++c) bv[c][s4] = bn[c][s4];
-    }
-  }
-  // C/D map (gfx950, dtype-independent): col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
-  const uint32_t W = n_out + 1;
+// Epilogue of one wave's 32 x 32 accumulator tile (all 8 chunk sums) at rows row0 .., columns
+// col0 .. of the batch.  C/D map (gfx950, dtype-independent): col = lane & 31,
+// row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5).  Recombines the chunks, adds the body word (split 0
+// only) and stores, or adds atomically under split-K (pre-zeroed outputs; wrapping addition is
+// exact and order-free).
+__device__ __forceinline__ void ks_mfma_epilogue(const v16i (&acc)[8], uint32_t row0, uint32_t col0, int lane,
+                                                 const Rows<uint64_t> rout, const Rows<const uint64_t> rin,
+                                                 uint32_t n_in, uint32_t n_out, uint32_t num_samples, bool split, bool body) {
   const uint32_t j = col0 + (lane & 31);
-  if (j >= W) return;
+  if (j >= rout.width) return;
 #pragma unroll
-  for (int t = 0; t < RT; ++t)
+  for (int r = 0; r < 16; ++r) {
+    const uint32_t b = row0 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+    if (b >= num_samples) continue;
+    uint64_t sum = 0ull;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const uint32_t b = row0 + 32 * t + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-      if (b >= num_samples) continue;
-      uint64_t sum = 0ull;
-#pragma unroll
-      for (int c = 0; c < 8; ++c) sum += (uint64_t)(int64_t)acc[t][c][r] << (8 * c);
-      uint64_t v = 0ull - sum;
-      if (j == n_out && blockIdx.z == 0) v += in[(in_idx ? in_idx[b] : b) * (uint64_t)(n_in + 1) + n_in];
-      uint64_t* o = out + (out_idx ? out_idx[b] : b) * (uint64_t)W + j;
-      if (split) atomicAdd((unsigned long long*)o, (unsigned long long)v);
-      else *o = v;
-    }
+    for (int c = 0; c < 8; ++c) sum += (uint64_t)(int64_t)acc[c][r] << (8 * c);
+    uint64_t v = 0ull - sum;
+    if (j == n_out && body) v += rin.at(b, n_in);
+    uint64_t* o = &rout.at(b, j);
+    if (split) atomicAdd((unsigned long long*)o, (unsigned long long)v);
+    else *o = v;
+  }
 }
 
-// LDS-staged form (KS_LDS): 8 waves share a 128-sample x 64-word tile; each 64-k block of the
-// tile's operands (digits 8 KB + key bytes 32 KB) is brought into an LDS ring of 3 stages by
-// LDS-DMA (2 stages in flight), so every operand byte crosses L2 -> CU once per workgroup instead
-// of once per wave.  LDS layout of a stage: A[kc][row] and B[c][kc][col], 16-byte cells, kc =
-// 16-byte k chunk: each DMA piece (64 lanes x 16 B) is one (kc, 64 rows / cols) run, and a
-// fragment read (lanes along rows / columns) is conflict-free.
-#ifndef KS_LDS
-#define KS_LDS 1
-#endif
-constexpr int KSL_ROWS = 128, KSL_COLS = 64, KSL_KB = 64, KSL_RS = 3;
+// 8 waves share a 128-sample x 64-word tile, one 32 x 32 tile of all 8 chunks each (8 int32
+// accumulator tiles); each 64-k block of the tile's operands (digits 8 KB + key bytes 32 KB) is
+// brought into an LDS ring of 3 stages by LDS-DMA (2 stages in flight), so every operand byte
+// crosses L2 -> CU once per workgroup instead of once per wave.  LDS layout of a stage: A[kc][row]
+// and B[c][kc][col], 16-byte cells, kc = 16-byte k chunk: each DMA piece (64 lanes x 16 B) is one
+// (kc, 64 rows / cols) run, and a fragment read (lanes along rows / columns) is conflict-free.
+// Split-K (gridDim.z > 1): this workgroup sums k in [k_begin, k_end).
 constexpr int KSL_A_CELLS = (KSL_KB / 16) * KSL_ROWS;                 // 512 cells = 8 KB
 constexpr int KSL_STAGE_CELLS = KSL_A_CELLS + 8 * (KSL_KB / 16) * KSL_COLS;  // + 2048 cells = 32 KB
 constexpr int KSL_PIECES = KSL_STAGE_CELLS / 64;                      // 40 DMA pieces per stage
@@ -398,117 +355,8 @@ __global__ void __launch_bounds__(512) ks_mfma_lds_kernel(uint64_t* __restrict__
       for (int c = 0; c < 8; ++c) acc[c] = __builtin_amdgcn_mfma_i32_32x32x32_i8(av, bv[c], acc[c], 0, 0, 0);
     }
   }
-  const uint32_t W = n_out + 1;
-  const uint32_t j = col_base + 32 * ct + r32;
-  if (j >= W) return;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const uint32_t b = row_base + 32 * rt + (r & 3) + 8 * (r >> 2) + 4 * h;
-    if (b >= num_samples) continue;
-    uint64_t sum = 0ull;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) sum += (uint64_t)(int64_t)acc[c][r] << (8 * c);
-    uint64_t v = 0ull - sum;
-    if (j == n_out && blockIdx.z == 0) v += in[(in_idx ? in_idx[b] : b) * (uint64_t)(n_in + 1) + n_in];
-    uint64_t* o = out + (out_idx ? out_idx[b] : b) * (uint64_t)W + j;
-    if (split) atomicAdd((unsigned long long*)o, (unsigned long long)v);
-    else *o = v;
-  }
-}
-
-// Four-wave form of the LDS-staged kernel (same stages, same operand layout): each wave covers 64
-// samples (two 32-row tiles) x 32 words, so every key-chunk fragment it reads from LDS serves two
-// MFMAs (16 per 32-k step from 10 fragment reads, against 8 from 9 in the eight-wave form): LDS
-// reads per MFMA fall from 1.125 to 0.625 fragments, for one wave per SIMD whose 256 accumulator
-// registers (AGPRs) leave room for the next step's fragments (read ahead of the MFMAs).
-constexpr int KSL4_PPW = KSL_PIECES / 4;  // 10 DMA pieces per wave per stage
-__global__ void __launch_bounds__(256) ks_mfma_lds4_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_idx,
-                                                         const uint64_t* __restrict__ in,
-                                                         const uint64_t* __restrict__ in_idx, const int8_t* __restrict__ A,
-                                                         const int8_t* __restrict__ Bt, uint32_t n_in, uint32_t n_out,
-                                                         uint32_t num_samples, uint32_t NP, uint32_t Kp,
-                                                         uint32_t Ks, uint32_t k_per_split) {
-  extern __shared__ __attribute__((aligned(16))) v4i lds[];
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int rh = w >> 1, ch = w & 1;  // rows 64 rh .. + 63 (two 32-row tiles), words 32 ch .. + 31
-  const uint32_t row_base = blockIdx.y * KSL_ROWS, col_base = blockIdx.x * KSL_COLS;
-  const uint32_t k_begin = blockIdx.z * k_per_split, k_end = min(Kp, k_begin + k_per_split);
-  const uint32_t nst = (k_end - k_begin) / KSL_KB;
-  const bool split = gridDim.z > 1;
-  const uint64_t cstride = (uint64_t)NP * Ks;
-  const int8_t* src[KSL4_PPW];
-  int dst[KSL4_PPW];
-#pragma unroll
-  for (int q = 0; q < KSL4_PPW; ++q) {
-    const int p = w * KSL4_PPW + q;
-    if (p < 8) {  // A: kc = p >> 1, rows 64 (p & 1) .. + 63
-      const int kc = p >> 1, r2 = p & 1;
-      src[q] = A + (uint64_t)(row_base + 64 * r2 + lane) * Ks + 16 * kc;
-      dst[q] = kc * KSL_ROWS + 64 * r2;
-    } else {  // B: c, kc
-      const int pb = p - 8, c = pb >> 2, kc = pb & 3;
-      src[q] = Bt + c * cstride + (uint64_t)(col_base + lane) * Ks + 16 * kc;
-      dst[q] = KSL_A_CELLS + (c * 4 + kc) * KSL_COLS;
-    }
-  }
-  auto issue = [&](uint32_t t) __attribute__((always_inline)) {
-    const uint32_t kb = k_begin + t * KSL_KB;
-    v4i* stage = lds + (t % KSL_RS) * KSL_STAGE_CELLS;
-#pragma unroll
-    for (int q = 0; q < KSL4_PPW; ++q)
-      __builtin_amdgcn_global_load_lds(reinterpret_cast<const void*>(src[q] + kb), (lds_ptr_t)(stage + dst[q]), 16, 0, 0);
-  };
-  v16i acc[2][8];
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int c = 0; c < 8; ++c)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[t][c][r] = 0;
-  if (nst > 0) issue(0);
-  if (nst > 1) issue(1);
-  const int r32 = lane & 31, h = lane >> 5;
-  for (uint32_t t = 0; t < nst; ++t) {
-    if (t + 1 < nst) wait_vmcnt<KSL4_PPW>();
-    else wait_vmcnt<0>();
-    pair_barrier();
-    if (t + 2 < nst) issue(t + 2);
-    const v4i* stage = lds + (t % KSL_RS) * KSL_STAGE_CELLS;
-    v4i av[2][2], bv[2][8];
-#pragma unroll
-    for (int s4 = 0; s4 < KSL_KB / 32; ++s4) {
-      const int kc = 2 * s4 + h;
-#pragma unroll
-      for (int rt = 0; rt < 2; ++rt) av[s4][rt] = stage[kc * KSL_ROWS + 64 * rh + 32 * rt + r32];
-#pragma unroll
-      for (int c = 0; c < 8; ++c) bv[s4][c] = stage[KSL_A_CELLS + (c * 4 + kc) * KSL_COLS + 32 * ch + r32];
-    }
-#pragma unroll
-    for (int s4 = 0; s4 < KSL_KB / 32; ++s4)
-#pragma unroll
-      for (int c = 0; c < 8; ++c)
-#pragma unroll
-        for (int rt = 0; rt < 2; ++rt)
-          acc[rt][c] = __builtin_amdgcn_mfma_i32_32x32x32_i8(av[s4][rt], bv[s4][c], acc[rt][c], 0, 0, 0);
-  }
-  const uint32_t W = n_out + 1;
-  const uint32_t j = col_base + 32 * ch + r32;
-  if (j >= W) return;
-#pragma unroll
-  for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const uint32_t b = row_base + 64 * rh + 32 * rt + (r & 3) + 8 * (r >> 2) + 4 * h;
-      if (b >= num_samples) continue;
-      uint64_t sum = 0ull;
-#pragma unroll
-      for (int c = 0; c < 8; ++c) sum += (uint64_t)(int64_t)acc[rt][c][r] << (8 * c);
-      uint64_t v = 0ull - sum;
-      if (j == n_out && blockIdx.z == 0) v += in[(in_idx ? in_idx[b] : b) * (uint64_t)(n_in + 1) + n_in];
-      uint64_t* o = out + (out_idx ? out_idx[b] : b) * (uint64_t)W + j;
-      if (split) atomicAdd((unsigned long long*)o, (unsigned long long)v);
-      else *o = v;
-    }
+  ks_mfma_epilogue(acc, row_base + 32 * rt, col_base + 32 * ct, lane, Rows<uint64_t>{out, out_idx, n_out + 1},
+                   Rows<const uint64_t>{in, in_idx, n_in + 1}, n_in, n_out, num_samples, split, blockIdx.z == 0);
 }
 
 // Whether the MFMA path is exact for these parameters (int8 digits, int32 sums): a sum has K =
@@ -553,14 +401,16 @@ static int8_t* key_bytes(const KsArgs& a, uint32_t K, uint32_t W, uint32_t NP, u
   int dev = 0;
   CHIP_CHECK(hipGetDevice(&dev));
   keep_pool_memory();
-  bool cache = key_cache_on();
-  if (cache) {
-    std::lock_guard<std::mutex> g(g_kb_mu);
-    cache = g_tracked.count(a.ksk) > 0;
-  }
+  // A tracked key holds g_kb_mu from the tracked check to the insert, so a release_key_bytes of
+  // the buffer on another thread falls before all of it or after all of it; any other key drops
+  // the lock at once.
   std::unique_lock<std::mutex> lk(g_kb_mu, std::defer_lock);
-  if (cache) {
+  if (key_cache_on()) {
     lk.lock();
+    if (!g_tracked.count(a.ksk)) lk.unlock();
+  }
+  const bool cache = lk.owns_lock();
+  if (cache) {
     for (const KeyBytes& e : g_kb)
       if (e.ksk == a.ksk && e.dev == dev && e.K == K && e.W == W && e.NP == NP && e.Ks == Ks) {
         CHIP_CHECK(hipStreamWaitEvent(a.stream, e.built, 0));
@@ -613,22 +463,49 @@ int release_key_bytes(const void* p, hipStream_t s, bool untrack) {
   return (int)gone.size();
 }
 
+// zeroes the output rows of a split-K call, whose workgroups add their partial sums atomically
+static void launch_zero(const KsArgs& a) {
+  const uint64_t total = (uint64_t)(a.n_out + 1) * a.num_samples;
+  hipLaunchKernelGGL(keyswitch_zero_kernel, dim3((uint32_t)std::min<uint64_t>((total + 255) / 256, 4096)), dim3(256),
+                     0, a.stream, a.out, a.out_idx, a.n_out + 1, a.num_samples);
+}
+
+// what the launches since the last check left: 0, or -1 with the error recorded
+static int launch_status() {
+  const hipError_t e = hipGetLastError();
+  if (e == hipSuccess) return 0;
+  set_error("keyswitch launch failed: %s", hipGetErrorString(e));
+  return -1;
+}
+
+// samples [s0, s0 + cn) of a call as a call of their own: the index arrays shifted where given,
+// else the row pointers
+static KsArgs pass_args(const KsArgs& a, uint32_t s0, uint32_t cn) {
+  KsArgs p = a;
+  p.num_samples = cn;
+  if (a.in_idx) p.in_idx += s0;
+  else p.in += (uint64_t)s0 * (a.n_in + 1);
+  if (a.out_idx) p.out_idx += s0;
+  else p.out += (uint64_t)s0 * (a.n_out + 1);
+  return p;
+}
+
 static int keyswitch_mfma_launch(const KsArgs& a) {
-  const uint32_t W = a.n_out + 1, NP = (W + KSM_COLS - 1) / KSM_COLS * KSM_COLS;
-  const uint32_t K = a.n_in * a.level, kb = (K + KSM_KB - 1) / KSM_KB;
+  const uint32_t W = a.n_out + 1, NP = (W + KSL_COLS - 1) / KSL_COLS * KSL_COLS;
+  const uint32_t K = a.n_in * a.level, kb = (K + KSL_KB - 1) / KSL_KB;
   // samples per pass: the int8 digit matrix of a pass stays <= 1 GiB (8-bit rows: K = 81,920);
-  // rows are Ks = (kb + 7) KSM_KB bytes apart (below)
-  const uint64_t kmax = (uint64_t)(kb + 7) * KSM_KB;
+  // rows are Ks = (kb + 7) KSL_KB bytes apart (below)
+  const uint64_t kmax = (uint64_t)(kb + 7) * KSL_KB;
   // (CONCRETE_HIP_KS_CHUNK: a smaller pass size, read per call — the multi-pass test uses it)
   const char* cap_env = getenv("CONCRETE_HIP_KS_CHUNK");
   const uint64_t cap = cap_env && atoll(cap_env) > 0 ? (uint64_t)atoll(cap_env) : (1ull << 30) / kmax;
   const uint32_t chunk = (uint32_t)std::max<uint64_t>(
-      KSM_ROWS, std::min<uint64_t>((uint64_t)(a.num_samples + KSM_ROWS - 1) / KSM_ROWS * KSM_ROWS,
-                                   cap / KSM_ROWS * KSM_ROWS));
-  // split K over s workgroups so that the rounds of the chip (one workgroup per CU: 512 registers
-  // x 4 waves, or 120 KB of LDS) come out even: time ~ ceil(wgs s / 256) / s, smallest s on ties
+      KSL_ROWS, std::min<uint64_t>((uint64_t)(a.num_samples + KSL_ROWS - 1) / KSL_ROWS * KSL_ROWS,
+                                   cap / KSL_ROWS * KSL_ROWS));
+  // split K over s workgroups so that the rounds of the chip (one workgroup per CU: 120 KB of
+  // LDS) come out even: time ~ ceil(wgs s / 256) / s, smallest s on ties
   // (cfg2 batch 4096: 320 workgroups -> s = 4, 5 full rounds)
-  const uint32_t wgs = (NP / KSM_COLS) * (chunk / KSM_ROWS);
+  const uint32_t wgs = (NP / KSL_COLS) * (chunk / KSL_ROWS);
   uint32_t splits = 1;
   {
     double best = 1e30;
@@ -637,18 +514,14 @@ static int keyswitch_mfma_launch(const KsArgs& a) {
       if (t < best - 1e-9) best = t, splits = sp;
     }
   }
-  const uint32_t k_per_split = (kb + splits - 1) / splits * KSM_KB;
-  splits = (kb * KSM_KB + k_per_split - 1) / k_per_split;
+  const uint32_t k_per_split = (kb + splits - 1) / splits * KSL_KB;
+  splits = (kb * KSL_KB + k_per_split - 1) / k_per_split;
   const uint32_t Kp = splits * k_per_split;  // zero padded: whole blocks in every split
   // operand row stride: covers the padding of any split count (<= 8), so one key-byte layout
   // serves every batch size
-  const uint32_t Ks = (kb + 7) * KSM_KB;
-  static_assert(KSL_ROWS == KSM_ROWS && KSL_COLS == KSM_COLS && KSL_KB == KSM_KB, "one padding for both kernels");
-  // CONCRETE_HIP_KS_WAVES=4: the four-wave LDS kernel (A/B), read per call
-  const char* kw = getenv("CONCRETE_HIP_KS_WAVES");
-  const bool four = KS_LDS && kw && atoi(kw) == 4;
-  if (KS_LDS) CHIP_CHECK(hipFuncSetAttribute(four ? (const void*)ks_mfma_lds4_kernel : (const void*)ks_mfma_lds_kernel,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)KSL_LDS));
+  const uint32_t Ks = (kb + 7) * KSL_KB;
+  CHIP_CHECK(hipFuncSetAttribute((const void*)ks_mfma_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 (int)KSL_LDS));
   keep_pool_memory();
   // test hook: refuse operand scratch above this many bytes (the VALU fallback then runs)
   if (const char* lim = getenv("CONCRETE_HIP_KS_SCRATCH_LIMIT"))
@@ -664,39 +537,19 @@ static int keyswitch_mfma_launch(const KsArgs& a) {
   }
   const uint32_t ipr = (Ks + a.level - 1) / a.level;  // positions per digit row (covers the padding)
   for (uint32_t s0 = 0; s0 < a.num_samples; s0 += chunk) {
-    const uint32_t cn = std::min(chunk, a.num_samples - s0);
-    const uint32_t Bp = (cn + KSM_ROWS - 1) / KSM_ROWS * KSM_ROWS;
-    // this pass's rows: shift the index arrays when given, else the row pointers
-    const uint64_t* in_idx = a.in_idx ? a.in_idx + s0 : nullptr;
-    const uint64_t* out_idx = a.out_idx ? a.out_idx + s0 : nullptr;
-    const uint64_t* in = a.in_idx ? a.in : a.in + (uint64_t)s0 * (a.n_in + 1);
-    uint64_t* out = a.out_idx ? a.out : a.out + (uint64_t)s0 * W;
+    const KsArgs p = pass_args(a, s0, std::min(chunk, a.num_samples - s0));
+    const uint32_t Bp = (p.num_samples + KSL_ROWS - 1) / KSL_ROWS * KSL_ROWS;
     const uint64_t nd = (uint64_t)Bp * ipr;
-    hipLaunchKernelGGL(ks_digits_i8_kernel, dim3((uint32_t)((nd + 255) / 256)), dim3(256), 0, a.stream, A, in, in_idx,
-                       a.n_in, a.level, a.base_log, cn, Ks, ipr);
-    if (splits > 1) {
-      const uint64_t total = (uint64_t)W * cn;
-      hipLaunchKernelGGL(keyswitch_zero_kernel, dim3((uint32_t)std::min<uint64_t>((total + 255) / 256, 4096)),
-                         dim3(256), 0, a.stream, out, out_idx, W, cn);
-    }
-    if (four)
-      hipLaunchKernelGGL(ks_mfma_lds4_kernel, dim3(NP / KSL_COLS, Bp / KSL_ROWS, splits), dim3(256), KSL_LDS, a.stream,
-                         out, out_idx, in, in_idx, A, Bt, a.n_in, a.n_out, cn, NP, Kp, Ks, k_per_split);
-    else if (KS_LDS)
-      hipLaunchKernelGGL(ks_mfma_lds_kernel, dim3(NP / KSL_COLS, Bp / KSL_ROWS, splits), dim3(512), KSL_LDS, a.stream,
-                         out, out_idx, in, in_idx, A, Bt, a.n_in, a.n_out, cn, NP, Kp, Ks, k_per_split);
-    else
-      hipLaunchKernelGGL(ks_mfma_kernel, dim3(NP / KSM_COLS, Bp / KSM_ROWS, splits), dim3(256), 0, a.stream, out,
-                         out_idx, in, in_idx, A, Bt, a.n_in, a.n_out, cn, NP, Kp, Ks, k_per_split);
+    hipLaunchKernelGGL(ks_digits_i8_kernel, dim3((uint32_t)((nd + 255) / 256)), dim3(256), 0, p.stream, A, p.in,
+                       p.in_idx, p.n_in, p.level, p.base_log, p.num_samples, Ks, ipr);
+    if (splits > 1) launch_zero(p);
+    hipLaunchKernelGGL(ks_mfma_lds_kernel, dim3(NP / KSL_COLS, Bp / KSL_ROWS, splits), dim3(512), KSL_LDS, p.stream,
+                       p.out, p.out_idx, p.in, p.in_idx, A, Bt, p.n_in, p.n_out, p.num_samples, NP, Kp, Ks, k_per_split);
   }
-  hipError_t e = hipGetLastError();
+  const int rc = launch_status();
   CHIP_CHECK(hipFreeAsync(A, a.stream));
   if (bt_owned) CHIP_CHECK(hipFreeAsync(Bt, a.stream));
-  if (e != hipSuccess) {
-    set_error("keyswitch launch failed: %s", hipGetErrorString(e));
-    return -1;
-  }
-  return 0;
+  return rc;
 }
 
 // parameters the keyswitch kernels accept (64-bit arithmetic: the arguments may come from an
@@ -704,6 +557,25 @@ static int keyswitch_mfma_launch(const KsArgs& a) {
 bool keyswitch_params_ok(uint32_t level, uint32_t base_log, uint32_t n_in, uint32_t n_out) {
   return level >= 1 && base_log >= 1 && (uint64_t)level * base_log < 64 && n_in >= 1 &&
          (uint64_t)n_out + 1 <= KS_MAX_ROW;
+}
+
+// keyswitch_kernel<U, split, nch> for run-time U = 1 .. KS_MAX_U, nch = 3, 4 or 0
+using valu_kernel_t = decltype(&keyswitch_kernel<1, false, 0>);
+template <int U, int NCH>
+static valu_kernel_t valu_kernel(bool split) {
+  return split ? keyswitch_kernel<U, true, NCH> : keyswitch_kernel<U, false, NCH>;
+}
+template <int U>
+static valu_kernel_t valu_kernel(bool split, int nch) {
+  return nch == 3 ? valu_kernel<U, 3>(split) : nch == 4 ? valu_kernel<U, 4>(split) : valu_kernel<U, 0>(split);
+}
+static valu_kernel_t valu_kernel(uint32_t U, bool split, int nch) {
+  switch (U) {
+    case 1: return valu_kernel<1>(split, nch);
+    case 2: return valu_kernel<2>(split, nch);
+    case 3: return valu_kernel<3>(split, nch);
+    default: return valu_kernel<4>(split, nch);
+  }
 }
 
 int keyswitch_launch(const KsArgs& a) {
@@ -726,11 +598,7 @@ int keyswitch_launch(const KsArgs& a) {
   if (blocks < 512) splits = std::min<uint32_t>((512 + blocks - 1) / blocks, std::max<uint32_t>(1, a.n_in / 128));
   const uint32_t per = ((a.n_in + splits - 1) / splits + KS_ICHUNK - 1) / KS_ICHUNK * KS_ICHUNK;
   splits = (a.n_in + per - 1) / per;
-  if (splits > 1) {
-    const uint64_t total = (uint64_t)(a.n_out + 1) * a.num_samples;
-    hipLaunchKernelGGL(keyswitch_zero_kernel, dim3((uint32_t)std::min<uint64_t>((total + 255) / 256, 4096)), dim3(256),
-                       0, a.stream, a.out, a.out_idx, a.n_out + 1, a.num_samples);
-  }
+  if (splits > 1) launch_zero(a);
   // int32 chunk sums of one block: FP * dmax * (max chunk) <= 2^31 - 1 with dmax = l 2^(logB-1)
   // (the largest digit row sum): 3 chunks (<= 22 bits, FP = 16) when dmax <= 32, 4 chunks
   // (16 bits, FP = 32) when dmax <= 1024, else the 64-bit products.  Compared by division so
@@ -738,36 +606,9 @@ int keyswitch_launch(const KsArgs& a) {
   const uint64_t dmax = a.base_log - 1 >= 40 ? ~0ull : (1ull << (a.base_log - 1)) * a.level;
   const int nch = dmax <= 0x7fffffffull / (16ull * ((1ull << 22) - 1)) ? 3
                   : dmax <= 0x7fffffffull / ((uint64_t)KS_ICHUNK * 65535ull) ? 4 : 0;
-#define KS_LAUNCH2(UU, CH)                                                                                         \
-  if (splits > 1)                                                                                                  \
-    hipLaunchKernelGGL((keyswitch_kernel<UU, true, CH>), dim3(blocks, splits, zw), dim3(KS_THREADS), 0, a.stream,     \
-                       a.out, a.out_idx, a.in, a.in_idx, a.ksk, a.n_in, a.n_out, a.base_log, a.level,              \
-                       a.num_samples, per);                                                                        \
-  else                                                                                                             \
-    hipLaunchKernelGGL((keyswitch_kernel<UU, false, CH>), dim3(blocks, 1, zw), dim3(KS_THREADS), 0, a.stream, a.out,     \
-                       a.out_idx, a.in, a.in_idx, a.ksk, a.n_in, a.n_out, a.base_log, a.level, a.num_samples, per)
-#define KS_LAUNCH(UU)          \
-  if (nch == 3) {              \
-    KS_LAUNCH2(UU, 3);         \
-  } else if (nch == 4) {       \
-    KS_LAUNCH2(UU, 4);         \
-  } else {                     \
-    KS_LAUNCH2(UU, 0);         \
-  }
-  switch (U) {
-    case 1: KS_LAUNCH(1); break;
-    case 2: KS_LAUNCH(2); break;
-    case 3: KS_LAUNCH(3); break;
-    default: KS_LAUNCH(4); break;
-  }
-#undef KS_LAUNCH
-#undef KS_LAUNCH2
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("keyswitch launch failed: %s", hipGetErrorString(e));
-    return -1;
-  }
-  return 0;
+  hipLaunchKernelGGL(valu_kernel(U, splits > 1, nch), dim3(blocks, splits, zw), dim3(KS_THREADS), 0, a.stream, a.out,
+                     a.out_idx, a.in, a.in_idx, a.ksk, a.n_in, a.n_out, a.base_log, a.level, a.num_samples, per);
+  return launch_status();
 }
 
 }  // namespace chip

@@ -351,7 +351,7 @@ def test_keyswitch_decompositions(B, oracle, torch_cuda, ks_l, ks_logB):
 @pytest.mark.parametrize("ks_l,ks_logB,nb", [(4, 3, 64), (4, 3, 300), (7, 3, 129), (3, 4, 200), (5, 3, 96),
                                              (2, 7, 70), (1, 7, 65)])
 def test_keyswitch_mfma_path(B, oracle, torch_cuda, ks_l, ks_logB, nb):
-    """The int8 matrix-core keyswitch (keyswitch.hip ks_mfma_kernel: 8 balanced key bytes x int8
+    """The int8 matrix-core keyswitch (keyswitch.hip ks_mfma_lds_kernel: 8 balanced key bytes x int8
     digits, int32 sums, taken from 64 samples on when base_log <= 7): bit-exact vs the oracle,
     ragged batches (partial 64-row tiles), n + 1 = 631 output words (partial column tile), the
     widest accepted digits (logB = 7), and permuted in_idx / out_idx."""
@@ -605,11 +605,10 @@ def test_keyswitch_wide_output_rows(B, oracle, torch_cuda, n_out, ks_l, ks_logB,
 
 
 @pytest.mark.parametrize("ks_l,ks_logB,nb", [(4, 3, 4096), (4, 3, 300), (7, 3, 129), (2, 7, 70)])
-def test_keyswitch_mfma_four_wave_kernel(B, oracle, torch_cuda, monkeypatch, ks_l, ks_logB, nb):
-    """The four-wave LDS matrix-core keyswitch (CONCRETE_HIP_KS_WAVES=4: two 32-row tiles per wave,
-    each key fragment serving two MFMAs): bit-exact vs the oracle at the cfg2 batch (split-K
-    over 4 workgroups), ragged batches, the widest digits, and permuted index arrays."""
-    monkeypatch.setenv("CONCRETE_HIP_KS_WAVES", "4")
+def test_keyswitch_mfma_cfg2_batch_and_ragged(B, oracle, torch_cuda, ks_l, ks_logB, nb):
+    """The matrix-core keyswitch (ks_mfma_lds_kernel) bit-exact vs the oracle at the cfg2 batch
+    (4096 samples: 320 workgroups, split-K over 4), ragged batches, the widest digits, and a
+    permuted input index array."""
     p = replace(B.CFG2, ks_level=ks_l, ks_base_log=ks_logB)
     glwe_sk = B.binary_key(p.big_n, 9400 + ks_logB + ks_l)
     lwe_sk = B.binary_key(p.n, 9500 + ks_logB + ks_l)
@@ -631,6 +630,56 @@ def test_keyswitch_mfma_four_wave_kernel(B, oracle, torch_cuda, monkeypatch, ks_
     sel = rows[: min(len(rows), 64)]
     exp = oracle.keyswitch_batch(op, cts[in_idx[sel].astype(np.int64)], ksk)
     assert np.array_equal(B.to_host(out2)[sel], exp)
+
+
+def keyswitch_vs_oracle(B, oracle, torch, p, nb, seed, plain=True, indexed=False):
+    """One keyswitch of nb random ciphertexts under p, bit-exact vs the oracle: rows in order
+    (plain) and / or through permuted in_idx and out_idx arrays (indexed)."""
+    ksk = B.ksk_generate(p, B.binary_key(p.big_n, seed), B.binary_key(p.n, seed + 1), seed + 2)
+    rng = np.random.RandomState(seed)
+    cts = rng.randint(0, 2 ** 63, size=(nb, p.big_n + 1), dtype=np.int64).astype(np.uint64) * np.uint64(2) + \
+        np.uint64(1)
+    dev = "cuda:0"
+    d_ksk, d_in = B.to_device(ksk, dev), B.to_device(cts, dev)
+    ref = oracle.keyswitch_batch(oparams(oracle, p), cts, ksk)
+    if plain:
+        out = B.keyswitch(p, d_ksk, d_in)
+        torch.cuda.synchronize()
+        assert np.array_equal(B.to_host(out), ref)
+    if indexed:
+        in_idx = rng.permutation(nb).astype(np.uint64)
+        out_idx = rng.permutation(nb).astype(np.uint64)
+        out = B.keyswitch(p, d_ksk, d_in, in_idx=B.to_device(in_idx, dev), out_idx=B.to_device(out_idx, dev))
+        torch.cuda.synchronize()
+        exp = np.zeros_like(ref)
+        exp[out_idx.astype(np.int64)] = ref[in_idx.astype(np.int64)]
+        assert np.array_equal(B.to_host(out), exp)
+
+
+@pytest.mark.parametrize("ks_l,ks_logB", [(4, 3), (6, 6), (2, 11)])
+@pytest.mark.parametrize("n_in", [128, 1024])
+@pytest.mark.parametrize("row", [200, 400, 631, 1000])
+def test_keyswitch_valu_every_instantiation(B, oracle, torch_cuda, row, n_in, ks_l, ks_logB):
+    """All 24 keyswitch_kernel<U, SPLIT, NCH>, bit-exact vs the oracle: n_out + 1 = 200, 400, 631,
+    1000 words give U = 1..4 words per thread; n_in = 128 gives one split (n_in / 128 <= 1), 1024
+    gives 8 at this batch; (l, logB) = (4, 3), (6, 6), (2, 11) give three key chunks, four, and the
+    64-bit products.  11 samples (a full tile of 8 and a ragged 3, below the matrix-core path's
+    64); the 631-word split case of each chunk form also runs through permuted index arrays.
+    (Nothing on the keyswitch's way validates N, so n_in = 128 is simply k = 1, N = 128.)"""
+    p = replace(B.CFG2, k=1, N=n_in, n=row - 1, ks_level=ks_l, ks_base_log=ks_logB)
+    keyswitch_vs_oracle(B, oracle, torch_cuda, p, 11, 9700 + row + n_in + ks_logB,
+                        indexed=row == 631 and n_in == 1024)
+
+
+@pytest.mark.parametrize("n_in", [40, 128, 192, 256])
+def test_keyswitch_mfma_short_k(B, oracle, torch_cuda, n_in):
+    """The matrix-core kernel on short sums (l = 1, logB = 7, K = n_in): 40, 128, 192 give
+    kb = 1, 2, 3 blocks of 64, which run unsplit with an LDS ring of 1, 2, 3 stages (its prologue
+    and tail; 40 also pads K inside the block); 256 gives kb = 4, where the chooser takes 2 splits
+    of 2 stages.  65 samples (a full 64-row wave tile and one row), n_out + 1 = 631, with and
+    without index arrays, bit-exact vs the oracle."""
+    p = replace(B.CFG2, k=1, N=n_in, n=630, ks_level=1, ks_base_log=7)
+    keyswitch_vs_oracle(B, oracle, torch_cuda, p, 65, 9800 + n_in, plain=True, indexed=True)
 
 
 @pytest.mark.parametrize("cts_per_wg", [1, 2])
