@@ -471,7 +471,76 @@ __device__ __forceinline__ void slot_signal(uint32_t* ctr, int lane, uint32_t& c
   if (lane == 0) __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
-template <bool RESID, bool STAMPS>
+// ---- The step's integer pieces (kernel_util.hpp: rot_term / rot_state, decomp_level32, limb_add)
+//      with the decomposition base fixed at compile time (BL = base_log, L levels, L BL <= 27).
+//      Every shift, field offset and constant is an immediate, and the sequences are shorter ones
+//      that keep every digit and every accumulator word ("the integer path").
+__device__ __forceinline__ void pin(uint32_t& x) { asm volatile("" : "+v"(x)); }
+// The decomposer works on the UNSHIFTED word W = high word of ct1 + 2^(nrep-1), nrep = 64 - L BL:
+// the state of decomp_level32 is W >> (nrep - 32), so level q's field lies at 32 - (L - q) BL,
+// the top field ends at bit 31 and the bits below the first field are never read.
+// rot_word: W of a slot from its o = o0 + 512 m (rot_term), the value rv read at the rotated place
+// and the wave's own b.  With s = -(src < N) as a 64-bit mask the negation is (rv ^ s) - s: no
+// separate carry word.
+template <int NREP>
+__device__ __forceinline__ uint32_t rot_word(uint64_t rv, uint32_t o, uint64_t b) {
+  static_assert(NREP > 32 && NREP < 64, "only the high word is decomposed");
+  const uint32_t s32 = (uint32_t)__builtin_amdgcn_sbfe((int32_t)o, 13u, 1u);
+  const uint64_t s = ((uint64_t)s32 << 32) | s32;
+  return (uint32_t)((((rv ^ s) - s) + b) >> 32) + (1u << (NREP - 33));
+}
+// Digit of level q (decomp_level32's recurrence and tie rule) from W, as the f64 the transform
+// takes; W takes the carry.  With tc = top + B/2 - 1 added at the field's place, the field becomes
+// res + tc - B carry and the bits above it take the carry: the digit res - B carry is the new field
+// minus tc, and the new word is the next level's (its own field is not read again).  Above the
+// last level's field there is no tie bit (the state is below 2^(L BL + 1)): its digit is
+// res - B [res > B/2], which is minus the top field of 2^off - 1 - W taken signed (the negation
+// goes into the transform's first operands).
+template <int BL, int L>
+__device__ __forceinline__ double decomp_word_digit(uint32_t& W, int q) {
+  static_assert(BL >= 1 && L * BL <= 27, "the exact range of the N = 1024 kernels");
+  const uint32_t off = 32u - (uint32_t)((L - q) * BL);
+  if (q + 1 == L) return -(double)((int32_t)(((1u << off) - 1u) - W) >> off);
+  // the tie bit: the next level's top bit, <= bit 31 since q + 2 <= L
+  const uint32_t tc = __builtin_amdgcn_ubfe(W, off + 2u * BL - 1u, 1u) + ((1u << (BL - 1)) - 1u);
+  W += tc << off;
+  return (double)((int32_t)__builtin_amdgcn_ubfe(W, off, (uint32_t)BL) - (int32_t)tc);
+}
+// Recombination: limb 0's rounding constant (the only one of the three whose bits stay below 2^64:
+// MAGIC_ALL_3 == RND_MAGIC_BITS, high word only) is not subtracted per coefficient but cancelled
+// by limb 2's own rounding constant, RND_MAGIC + RND2_OFS: limb 2 enters at 2^43, i.e. its low
+// word at bit 11 of the high word, and RND2_OFS << 11 == -(RND_MAGIC_BITS >> 32) mod 2^32.  Both
+// constants are even multiples of the unit in the last place, so every rounding falls as before.
+static_assert(MAGIC_ALL_3 == RND_MAGIC_BITS && (uint32_t)RND_MAGIC_BITS == 0u, "limbs 1 and 2 shift their constant out");
+constexpr uint32_t RND2_OFS = (0u - (uint32_t)(RND_MAGIC_BITS >> 32)) >> (limb_shift(2) - 32);
+static_assert((uint32_t)(RND2_OFS << (limb_shift(2) - 32)) + (uint32_t)(RND_MAGIC_BITS >> 32) == 0u && RND2_OFS % 2 == 0,
+              "limb 2's constant removes limb 0's");
+template <int LR>
+constexpr double fixed_rnd_magic() { return LR == 2 ? RND_MAGIC + (double)RND2_OFS : RND_MAGIC; }
+// tr, ti: the rounded parts fixed_rnd_magic<LR>() - x; limb 2 touches the high word alone (one
+// 32-bit shift-add, pinned: left to itself the compiler widens it back to a 64-bit add)
+__device__ __forceinline__ void hi_word_shl_add(uint64_t& a, uint64_t bits, int sh) {
+  uint32_t hi = (uint32_t)(a >> 32) + ((uint32_t)bits << sh);
+  pin(hi);
+  a = (uint64_t)(uint32_t)a | ((uint64_t)hi << 32);
+}
+template <int LR>
+__device__ __forceinline__ void fixed_limb_add(uint64_t& are, uint64_t& aim, double tr, double ti) {
+  const uint64_t br = (uint64_t)__double_as_longlong(tr), bi = (uint64_t)__double_as_longlong(ti);
+  if constexpr (LR == 0) {
+    are += br, aim += bi;
+  } else if constexpr (LR == 1) {
+    are += br << limb_shift(1), aim += bi << limb_shift(1);
+  } else {
+    hi_word_shl_add(are, br, limb_shift(2) - 32);
+    hi_word_shl_add(aim, bi, limb_shift(2) - 32);
+  }
+}
+
+// BL: base_log fixed at compile time (the metric's 7), or 0 for a base read at run time.  With BL
+// the rotation, the decomposition and the recombination take the forms above (rot_word,
+// decomp_word_digit, fixed_limb_add); BL = 0 is the code as it was.
+template <int BL, bool RESID, bool STAMPS>
 __global__ void __launch_bounds__(PBS_PAIRS * 128, 2)
 pbs1024_pair_slot_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ out_idx,
                          const uint64_t* __restrict__ luts, const uint64_t* __restrict__ lut_idx,
@@ -537,8 +606,8 @@ pbs1024_pair_slot_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict_
     for (int m = 0; m < 16; ++m) B[m] = neg_acc_coeff(lut, h, lane, m, bt, active);
   }
 
-  const int nrep = 64 - L * (int)base_log;
-  const int logB = (int)base_log;
+  const int logB = BL ? BL : (int)base_log;
+  const int nrep = 64 - L * logB;
   const int32_t neg_base = -(1 << logB);
   const uint32_t half_m1 = (1u << (logB - 1)) - 1u;
   double max_resid = 0.0;
@@ -570,19 +639,31 @@ pbs1024_pair_slot_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict_
       acc_t[7] += ai != 0ull && at != 0u;
     }
 
-    // ---- ct1 = B - X^{at} B and the decomposer state (pbs1024_pair_kernel)
+    // ---- ct1 = B - X^{at} B and the decomposer state (pbs1024_pair_kernel); with a fixed base the
+    //      unshifted word that holds it (rot_word)
     uint32_t st[16];
     {
       acc_to_scratch(xch64, lane, B);
       const uint32_t o0 = rot_o0(lane, at), khi = 1u << (nrep - 33);
+      // with a fixed base: one sum o0 + 512 m per slot, for the read's address and for the sign of
+      // the rotated term (pinned: the compiler otherwise forms the sign from a second sum)
+      uint32_t om[16];
+#pragma unroll
+      for (int m = 0; m < 16; ++m) {
+        om[m] = o0 + 512u * m;
+        if constexpr (BL != 0) pin(om[m]);
+      }
       // all 16 reads in flight at once (left to itself the scheduler issues them four at a time,
       // one LDS round trip each)
       uint64_t rv[16];
 #pragma unroll
-      for (int m = 0; m < 16; ++m) rv[m] = rot_read(xch64, o0, m);
+      for (int m = 0; m < 16; ++m) rv[m] = BL != 0 ? rot_read(xch64, om[m], 0) : rot_read(xch64, o0, m);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int m = 0; m < 16; ++m) st[m] = rot_state(rot_term(rv[m], o0, m) + B[m], khi, nrep);
+      for (int m = 0; m < 16; ++m) {
+        if constexpr (BL != 0) st[m] = rot_word<64 - L * BL>(rv[m], om[m], B[m]);
+        else st[m] = rot_state(rot_term(rv[m], o0, m) + B[m], khi, nrep);
+      }
       wave_lds_fence();
     }
     lap(0);
@@ -637,12 +718,20 @@ pbs1024_pair_slot_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict_
       window_send(Y, COc);
     };
     auto digits = [&](cplx (&v)[8], int q) __attribute__((always_inline)) {
-      int32_t d[16];
+      if constexpr (BL != 0) {
+        double d[16];
 #pragma unroll
-      for (int m = 0; m < 16; ++m)
-        d[m] = decomp_level32(st[m], (uint32_t)(q * logB), logB, half_m1, neg_base, q + 1 < L);
+        for (int m = 0; m < 16; ++m) d[m] = decomp_word_digit<BL, L>(st[m], q);
 #pragma unroll
-      for (int m = 0; m < 8; ++m) v[m] = {(double)d[m], (double)d[m + 8]};
+        for (int m = 0; m < 8; ++m) v[m] = {d[m], d[m + 8]};
+      } else {
+        int32_t d[16];
+#pragma unroll
+        for (int m = 0; m < 16; ++m)
+          d[m] = decomp_level32(st[m], (uint32_t)(q * logB), logB, half_m1, neg_base, q + 1 < L);
+#pragma unroll
+        for (int m = 0; m < 8; ++m) v[m] = {(double)d[m], (double)d[m + 8]};
+      }
     };
     cplx Y0[P];  // window (limb 0, output 0), begun inside the third transform
     cplx hold[8];  // the level-0 spectrum during the second transform
@@ -706,9 +795,11 @@ pbs1024_pair_slot_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict_
     // product c u is rounded once, into the integer (RND_MAGIC - c u as one FMA).
     auto recombine = [&](const cplx (&v)[8], auto LIc) __attribute__((always_inline)) {
       constexpr int lr = decltype(LIc)::value;
+      // with a fixed base limb 2's rounding constant also removes limb 0's (fixed_limb_add)
+      constexpr double RND = BL != 0 ? fixed_rnd_magic<lr>() : RND_MAGIC;
       // an FMA takes one scalar constant: the rounding constant goes through a vector register
       // pair, set here instead of held for the whole step loop
-      double rnd = RND_MAGIC;
+      double rnd = RND;
       pin(rnd);
 #pragma unroll
       for (int m = 0; m < 8; ++m) {
@@ -723,20 +814,21 @@ pbs1024_pair_slot_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict_
           if constexpr (RESID) {  // the residual is taken on the value that is rounded
             double pr = c * ur, pi = c * ui;
             pin(pr), pin(pi);
-            tr = RND_MAGIC - pr, ti = RND_MAGIC - pi;
-            max_resid = fmax(max_resid, fabs(pr - (RND_MAGIC - tr)));
-            max_resid = fmax(max_resid, fabs(pi - (RND_MAGIC - ti)));
+            tr = RND - pr, ti = RND - pi;
+            max_resid = fmax(max_resid, fabs(pr - (RND - tr)));
+            max_resid = fmax(max_resid, fabs(pi - (RND - ti)));
           } else {
             tr = __builtin_fma(-c, ur, rnd), ti = __builtin_fma(-c, ui, rnd);
           }
         } else {
-          tr = RND_MAGIC - v[m].re, ti = RND_MAGIC - v[m].im;
+          tr = RND - v[m].re, ti = RND - v[m].im;
           if constexpr (RESID) {
-            max_resid = fmax(max_resid, fabs(v[m].re - (RND_MAGIC - tr)));
-            max_resid = fmax(max_resid, fabs(v[m].im - (RND_MAGIC - ti)));
+            max_resid = fmax(max_resid, fabs(v[m].re - (RND - tr)));
+            max_resid = fmax(max_resid, fabs(v[m].im - (RND - ti)));
           }
         }
-        limb_add<lr>(B[m], B[m + 8], tr, ti);
+        if constexpr (BL != 0) fixed_limb_add<lr>(B[m], B[m + 8], tr, ti);
+        else limb_add<lr>(B[m], B[m + 8], tr, ti);
       }
     };
     // The first window of limb li + 1 runs between the reads of limb li's Y and its inverse, so the
@@ -836,7 +928,7 @@ static bool stamps_build() {
   return stamps;
 }
 
-template <bool RESID, bool STAMPS>
+template <int BL, bool RESID, bool STAMPS>
 static int launch_slot_t(const PbsArgs& a) {
   constexpr int P = PBS_PAIRS;
   const size_t lds = pbs1024_pair_slot_lds_bytes();
@@ -845,14 +937,17 @@ static int launch_slot_t(const PbsArgs& a) {
     set_error("pbs: N=1024 l=3 logB=%u is outside the exact range", a.base_log);
     return -2;
   }
-  return launch_fused(pbs1024_pair_slot_kernel<RESID, STAMPS>, P, P * 128, lds, a);
+  return launch_fused(pbs1024_pair_slot_kernel<BL, RESID, STAMPS>, P, P * 128, lds, a);
 }
 
 // the slot-split kernel (4 ciphertexts per workgroup, l = 3); with CONCRETE_HIP_PBS_STAMPS=1 its
-// instrumented build (`resid`: 8 * ceil(num_samples / 4) * NSTAMP u64)
+// instrumented build (`resid`: 8 * ceil(num_samples / 4) * NSTAMP u64).  base_log 7 (cfg2) runs the
+// instance with the base fixed at compile time; every other base of the exact range, and the
+// instrumented build, the one that reads it at run time.
 static int launch_slot(const PbsArgs& a) {
-  if (stamps_build()) return launch_slot_t<true, true>(a);
-  return a.resid ? launch_slot_t<true, false>(a) : launch_slot_t<false, false>(a);
+  if (stamps_build()) return launch_slot_t<0, true, true>(a);
+  if (a.base_log == 7) return a.resid ? launch_slot_t<7, true, false>(a) : launch_slot_t<7, false, false>(a);
+  return a.resid ? launch_slot_t<0, true, false>(a) : launch_slot_t<0, false, false>(a);
 }
 
 template <int P, int L, bool RESID, bool STAMPS>
