@@ -52,7 +52,7 @@ void set_error(const char* fmt, ...) {
 }
 const char* last_error() { return g_err; }
 
-static void die(const char* what) {
+void die(const char* what) {
   fprintf(stderr, "concrete-hip: %s: %s\n", what, g_err);
   abort();
 }
@@ -65,6 +65,24 @@ struct KeyEntry {
 };
 static std::mutex g_keys_mu;
 static std::unordered_map<const void*, KeyEntry> g_keys;
+
+// The Fourier key registered for `dest`, or nullptr for a pointer that is not registered.  The device
+// format follows the conversion's (n, k, l, N): a call with other parameters would read past the key
+// or reinterpret its layout, and dies in `what`.
+static const void* registered_key(const char* what, const void* dest, uint32_t gpu, uint32_t n, uint32_t k,
+                                  uint32_t level, uint32_t N) {
+  std::lock_guard<std::mutex> g(g_keys_mu);
+  auto it = g_keys.find(dest);
+  if (it == g_keys.end()) return nullptr;
+  const KeyEntry& e = it->second;
+  if (e.n != n || e.k != k || e.level != level || e.N != N || e.gpu != gpu) {
+    set_error("bootstrapping key converted for n=%u k=%u level=%u N=%u on gpu %u, called with n=%u k=%u level=%u "
+              "N=%u on gpu %u",
+              e.n, e.k, e.level, e.N, e.gpu, n, k, level, N, gpu);
+    die(what);
+  }
+  return e.fourier;
+}
 
 static void set_device(uint32_t gpu) { CHIP_CHECK(hipSetDevice((int)gpu)); }
 
@@ -107,13 +125,10 @@ static uint32_t* status_word_locked(int gpu, hipStream_t s, bool create) {
   DevStatus& d = g_status[gpu];
   if (!d.slab) {
     if (!create) return nullptr;
-    int prev = 0;
-    CHIP_CHECK(hipGetDevice(&prev));
-    CHIP_CHECK(hipSetDevice(gpu));
+    DeviceScope dev(gpu);
     void* p = nullptr;
     CHIP_CHECK(hipMalloc(&p, (STATUS_SLOTS + 1) * sizeof(uint32_t)));
     CHIP_CHECK(hipMemset(p, 0, (STATUS_SLOTS + 1) * sizeof(uint32_t)));
-    CHIP_CHECK(hipSetDevice(prev));
     d.slab = (uint32_t*)p;
     d.used = 1;  // slot 0: null stream / overflow
   }
@@ -196,16 +211,13 @@ int take_device_status(int gpu) {
     slab = g_status[gpu].slab, used = g_status[gpu].used;
   }
   if (!slab) return 0;  // no PBS kernel has run on this device
-  int prev = 0;
-  CHIP_CHECK(hipGetDevice(&prev));  // the caller's current device is restored (torch shares it)
-  CHIP_CHECK(hipSetDevice(gpu));
+  DeviceScope dev(gpu);  // the caller's current device is restored (torch shares it)
   CHIP_CHECK(hipDeviceSynchronize());
   status_take_kernel<<<1, 256, 0, nullptr>>>(slab, used);
   CHIP_CHECK(hipGetLastError());
   uint32_t any = 0;
   CHIP_CHECK(hipMemcpy(&any, slab + STATUS_SLOTS, sizeof(uint32_t), hipMemcpyDeviceToHost));
   if (any) CHIP_CHECK(hipMemset(slab + STATUS_SLOTS, 0, sizeof(uint32_t)));
-  CHIP_CHECK(hipSetDevice(prev));
   return any ? status_error(gpu, any, "some stream") : 0;
 }
 
@@ -247,11 +259,8 @@ void release_stream_status(int gpu, hipStream_t s) {
     --d.live;
     w = d.slab + k;
     // cleared before the slot can be handed out again (the lock is held across the clear)
-    int prev = 0;
-    CHIP_CHECK(hipGetDevice(&prev));
-    CHIP_CHECK(hipSetDevice(gpu));
+    DeviceScope dev(gpu);
     CHIP_CHECK(hipMemset(w, 0, sizeof(uint32_t)));
-    CHIP_CHECK(hipSetDevice(prev));
     d.free_slots.push_back(k);
   }
 }
@@ -260,6 +269,72 @@ uint32_t status_slots_in_use(int gpu) {
   if (gpu < 0 || gpu >= STATUS_MAX_DEV) return 0;
   std::lock_guard<std::mutex> g(g_status_mu);
   return g_status[gpu].live;
+}
+
+// One key conversion on s into `dest`, in the format of (k, N, l) or (`general`) the general one: a host
+// source is staged in stream-ordered memory, and the key's measured spectrum is recorded against the
+// certified bound (keycheck.hip; synchronises s, as the reference does after its conversion,
+// context.h:110-113).  0; -2 with the key stored and recorded when no base_log could use it exactly;
+// the launch's code, nothing recorded, when it failed.
+static int convert_and_record(hipStream_t s, void* dest, const void* src, bool src_is_device, uint32_t n, uint32_t k,
+                              uint32_t level, uint32_t N, bool general) {
+  const KeyFormat f = general ? generic_key_format(k, N, level) : key_format(k, N, level);
+  const uint64_t* src_dev = (const uint64_t*)src;
+  void* tmp = nullptr;
+  keep_pool_memory();
+  if (!src_is_device) {
+    const uint64_t bytes = std_bsk_bytes(n, k, level, N);
+    CHIP_CHECK(hipMallocAsync(&tmp, bytes, s));
+    CHIP_CHECK(hipMemcpyAsync(tmp, src, bytes, hipMemcpyHostToDevice, s));
+    src_dev = (const uint64_t*)tmp;
+  }
+  ConvertArgs a{s, dest, src_dev, n, k, level, N, f.limbs, key_spectrum_sink(s)};
+  int rc = general ? convert_bsk_generic_launch(a) : convert_bsk_launch(a);
+  const int rs = key_spectrum_record(s, rc == 0 ? dest : nullptr, f, n, k, N, level, a.smax);
+  if (rc == 0) rc = rs;
+  else key_spectrum_forget(dest);
+  if (tmp) CHIP_CHECK(hipFreeAsync(tmp, s));
+  return rc;
+}
+
+// ---- scratch handed out by scratch_cuda_* calls, and a call's own (companion.hpp) --------
+int8_t* ScratchRegistry::allocate(uint32_t gpu, uint64_t bytes, void* stream) {
+  CHIP_CHECK(hipSetDevice((int)gpu));
+  keep_pool_memory();
+  void* p = nullptr;
+  CHIP_CHECK(hipMallocAsync(&p, bytes, (hipStream_t)stream));
+  std::lock_guard<std::mutex> g(mu_);
+  bytes_[p] = bytes;
+  return (int8_t*)p;
+}
+
+uint64_t ScratchRegistry::size_of(const char* what, const char* origin, const void* buffer) {
+  if (!buffer) return 0;
+  std::lock_guard<std::mutex> g(mu_);
+  auto it = bytes_.find(buffer);
+  if (it == bytes_.end()) {
+    set_error("buffer %p does not come from %s", buffer, origin);
+    die(what);
+  }
+  return it->second;
+}
+
+void ScratchRegistry::release(uint32_t gpu, int8_t** buffer, void* stream) {
+  if (!buffer || !*buffer) return;
+  CHIP_CHECK(hipSetDevice((int)gpu));
+  {
+    std::lock_guard<std::mutex> g(mu_);
+    bytes_.erase(*buffer);
+  }
+  CHIP_CHECK(hipFreeAsync(*buffer, (hipStream_t)stream));
+  *buffer = nullptr;
+}
+
+int scratch_refused(const char* who, const void* scratch, uint64_t scratch_bytes, uint64_t need) {
+  if (!scratch || (scratch_bytes >= need && !((uintptr_t)scratch & 15))) return 0;
+  set_error("%s: scratch of %llu bytes at %p; %llu bytes, 16-byte aligned, are needed", who,
+            (unsigned long long)scratch_bytes, scratch, (unsigned long long)need);
+  return -3;
 }
 
 // ---- general-format companion keys (pbs_needs_generic_key) ------------------------------
@@ -302,11 +377,8 @@ void release_std_source(const void* primary) {
   }
   if (c) {
     key_spectrum_forget(c);
-    int prev = 0;
-    CHIP_CHECK(hipGetDevice(&prev));
-    CHIP_CHECK(hipSetDevice(gpu));
+    DeviceScope dev(gpu);
     CHIP_CHECK(hipFree(c));
-    CHIP_CHECK(hipSetDevice(prev));
   }
 }
 
@@ -325,20 +397,8 @@ const void* generic_companion_key(const void* primary, uint32_t n, uint32_t k, u
   if (!bytes) return nullptr;
   void* d = nullptr;
   CHIP_CHECK(hipMalloc(&d, bytes));
-  const uint64_t std_bytes = (uint64_t)n * level * (k + 1) * (k + 1) * N * 8ull;
-  const uint64_t* src_dev = e.src;
-  void* tmp = nullptr;
-  if (!e.on_device) {
-    CHIP_CHECK(hipMalloc(&tmp, std_bytes));
-    CHIP_CHECK(hipMemcpyAsync(tmp, e.src, std_bytes, hipMemcpyHostToDevice, s));
-    src_dev = (const uint64_t*)tmp;
-  }
-  ConvertArgs a{s, d, src_dev, n, k, level, N, generic_key_format(k, N, level).limbs, key_spectrum_sink(s)};
-  int rc = convert_bsk_generic_launch(a);
-  const int rs = key_spectrum_record(s, rc == 0 ? d : nullptr, generic_key_format(k, N, level), n, k, N, level, a.smax);
-  if (rc == 0) rc = rs;
+  const int rc = convert_and_record(s, d, e.src, e.on_device, n, k, level, N, true);
   CHIP_CHECK(hipStreamSynchronize(s));
-  if (tmp) CHIP_CHECK(hipFree(tmp));
   if (rc != 0) {
     key_spectrum_forget(d);
     CHIP_CHECK(hipFree(d));
@@ -440,7 +500,10 @@ void cuda_memcpy_async_to_cpu(void* dest, const void* src, uint64_t size, void* 
   CHIP_CHECK(hipMemcpyAsync(dest, src, size, hipMemcpyDeviceToHost, (hipStream_t)stream));
 }
 
-static void release_registered(void* ptr) {
+// Everything the backend derived from device buffer `ptr`: the Fourier key registered for it (with its
+// companion), its spectrum record, its cached keyswitch key bytes (freed on s; untrack: ptr itself is
+// being freed).  Returns the number of key-byte entries released.
+static int release_derived(const void* ptr, hipStream_t s, bool untrack) {
   void* f = nullptr;
   {
     std::lock_guard<std::mutex> g(g_keys_mu);
@@ -455,32 +518,25 @@ static void release_registered(void* ptr) {
     key_spectrum_forget(f);
     CHIP_CHECK(hipFree(f));
   }
+  key_spectrum_forget(ptr);
+  return release_key_bytes(ptr, s, untrack);
 }
 
 void cuda_drop(void* ptr, uint32_t gpu_index) {
   if (!ptr) return;
   set_device(gpu_index);
-  release_registered(ptr);
-  release_key_bytes(ptr, nullptr, true);
-  key_spectrum_forget(ptr);
+  release_derived(ptr, nullptr, true);
   CHIP_CHECK(hipFree(ptr));
 }
 
 void cuda_drop_async(void* ptr, void* stream, uint32_t gpu_index) {
   if (!ptr) return;
   set_device(gpu_index);
-  release_registered(ptr);
-  release_key_bytes(ptr, (hipStream_t)stream, true);
-  key_spectrum_forget(ptr);
+  release_derived(ptr, (hipStream_t)stream, true);
   CHIP_CHECK(hipFreeAsync(ptr, (hipStream_t)stream));
 }
 
-int concrete_hip_release_device_buffer(const void* ptr) {
-  if (!ptr) return 0;
-  release_registered((void*)ptr);
-  key_spectrum_forget(ptr);
-  return release_key_bytes(ptr, nullptr, false);
-}
+int concrete_hip_release_device_buffer(const void* ptr) { return ptr ? release_derived(ptr, nullptr, false) : 0; }
 
 void cuda_synchronize_device(uint32_t gpu_index) {
   set_device(gpu_index);
@@ -581,29 +637,8 @@ int concrete_hip_convert_bsk(void* stream, uint32_t gpu_index, void* dest_fourie
     return -2;
   }
   set_device(gpu_index);
-  hipStream_t s = (hipStream_t)stream;
-  const uint64_t std_bytes =
-      (uint64_t)input_lwe_dim * level_count * (glwe_dim + 1) * (glwe_dim + 1) * polynomial_size * 8ull;
-  const uint64_t* src_dev = (const uint64_t*)src;
-  void* tmp = nullptr;
-  keep_pool_memory();
-  if (!src_is_device) {
-    CHIP_CHECK(hipMallocAsync(&tmp, std_bytes, s));
-    CHIP_CHECK(hipMemcpyAsync(tmp, src, std_bytes, hipMemcpyHostToDevice, s));
-    src_dev = (const uint64_t*)tmp;
-  }
-  ConvertArgs a{s, dest_fourier, src_dev, input_lwe_dim, glwe_dim, level_count, polynomial_size,
-                default_limbs(glwe_dim, polynomial_size, level_count), key_spectrum_sink(s)};
-  int rc = convert_bsk_launch(a);
-  // the key's measured spectrum against the certified bound (keycheck.hip; synchronises s, as the
-  // reference does after its conversion, context.h:110-113)
-  const int rs = key_spectrum_record(s, rc == 0 ? dest_fourier : nullptr,
-                                     key_format(glwe_dim, polynomial_size, level_count), input_lwe_dim, glwe_dim,
-                                     polynomial_size, level_count, a.smax);
-  if (rc == 0) rc = rs;
-  else key_spectrum_forget(dest_fourier);
-  if (tmp) CHIP_CHECK(hipFreeAsync(tmp, s));
-  return rc;
+  return convert_and_record((hipStream_t)stream, dest_fourier, src, src_is_device != 0, input_lwe_dim, glwe_dim,
+                            level_count, polynomial_size, false);
 }
 
 int concrete_hip_pbs(void* stream, uint32_t gpu_index, uint64_t* lwe_array_out, const uint64_t* lwe_output_indexes,
@@ -659,33 +694,14 @@ int concrete_hip_convert_bsk_generic(void* stream, uint32_t gpu_index, void* des
     set_error("convert_bsk_generic: null pointer");
     return -1;
   }
-  const KeyFormat f = generic_key_format(glwe_dim, polynomial_size, level_count);
-  if (f.kind != KeyKind::GENERIC) {
+  if (generic_key_format(glwe_dim, polynomial_size, level_count).kind != KeyKind::GENERIC) {
     set_error("convert_bsk_generic: k=%u N=%u level=%u is not on the general path", glwe_dim, polynomial_size,
               level_count);
     return -2;
   }
   set_device(gpu_index);
-  hipStream_t s = (hipStream_t)stream;
-  const uint64_t std_bytes =
-      (uint64_t)input_lwe_dim * level_count * (glwe_dim + 1) * (glwe_dim + 1) * polynomial_size * 8ull;
-  const uint64_t* src_dev = (const uint64_t*)src;
-  void* tmp = nullptr;
-  keep_pool_memory();
-  if (!src_is_device) {
-    CHIP_CHECK(hipMallocAsync(&tmp, std_bytes, s));
-    CHIP_CHECK(hipMemcpyAsync(tmp, src, std_bytes, hipMemcpyHostToDevice, s));
-    src_dev = (const uint64_t*)tmp;
-  }
-  ConvertArgs a{s, dest, src_dev, input_lwe_dim, glwe_dim, level_count, polynomial_size, f.limbs,
-                key_spectrum_sink(s)};
-  int rc = convert_bsk_generic_launch(a);
-  const int rs = key_spectrum_record(s, rc == 0 ? dest : nullptr, f, input_lwe_dim, glwe_dim, polynomial_size,
-                                     level_count, a.smax);
-  if (rc == 0) rc = rs;
-  else key_spectrum_forget(dest);
-  if (tmp) CHIP_CHECK(hipFreeAsync(tmp, s));
-  return rc;
+  return convert_and_record((hipStream_t)stream, dest, src, src_is_device != 0, input_lwe_dim, glwe_dim, level_count,
+                            polynomial_size, true);
 }
 
 int concrete_hip_pbs_generic(void* stream, uint32_t gpu_index, uint64_t* lwe_array_out,
@@ -748,9 +764,8 @@ void cuda_convert_lwe_programmable_bootstrap_key_64(void* stream, uint32_t gpu_i
   CHIP_CHECK(hipMalloc(&f, bytes));
   // dest (caller-sized at n*l*(k+1)^2*N*8 bytes) receives the standard key verbatim and is the
   // conversion source; the Fourier form (larger: exact limbs) lives in the registry.
-  const uint64_t std_bytes =
-      (uint64_t)input_lwe_dim * level_count * (glwe_dim + 1) * (glwe_dim + 1) * polynomial_size * 8ull;
-  CHIP_CHECK(hipMemcpyAsync(dest, src, std_bytes, hipMemcpyHostToDevice, (hipStream_t)stream));
+  CHIP_CHECK(hipMemcpyAsync(dest, src, std_bsk_bytes(input_lwe_dim, glwe_dim, level_count, polynomial_size),
+                            hipMemcpyHostToDevice, (hipStream_t)stream));
   if (concrete_hip_convert_bsk(stream, gpu_index, f, dest, 1, input_lwe_dim, glwe_dim, level_count,
                                polynomial_size) != 0)
     die("cuda_convert_lwe_programmable_bootstrap_key_64");
@@ -812,27 +827,13 @@ void cuda_programmable_bootstrap_lwe_ciphertext_vector_64(
     set_error("num_many_lut=%u lut_stride=%u (only 1, 1 is used by the runtime)", num_many_lut, lut_stride);
     die("cuda_programmable_bootstrap_lwe_ciphertext_vector_64");
   }
-  KeyEntry e{};
-  {
-    std::lock_guard<std::mutex> g(g_keys_mu);
-    auto it = g_keys.find(bootstrapping_key);
-    if (it != g_keys.end()) e = it->second;
-  }
-  if (!e.fourier) {
+  const void* f = registered_key("cuda_programmable_bootstrap_lwe_ciphertext_vector_64", bootstrapping_key, gpu_index,
+                                 lwe_dimension, glwe_dimension, level_count, polynomial_size);
+  if (!f) {
     set_error("bootstrapping key %p was not converted by cuda_convert_lwe_programmable_bootstrap_key_64",
               bootstrapping_key);
     die("cuda_programmable_bootstrap_lwe_ciphertext_vector_64");
   }
-  // the device format follows the conversion's (n, k, l, N): a call with other parameters would
-  // read past the key or reinterpret its layout
-  if (e.n != lwe_dimension || e.k != glwe_dimension || e.level != level_count || e.N != polynomial_size ||
-      e.gpu != gpu_index) {
-    set_error("bootstrapping key converted for n=%u k=%u level=%u N=%u on gpu %u, called with n=%u k=%u level=%u "
-              "N=%u on gpu %u",
-              e.n, e.k, e.level, e.N, e.gpu, lwe_dimension, glwe_dimension, level_count, polynomial_size, gpu_index);
-    die("cuda_programmable_bootstrap_lwe_ciphertext_vector_64");
-  }
-  const void* f = e.fourier;
   if (concrete_hip_pbs(stream, gpu_index, (uint64_t*)lwe_array_out, (const uint64_t*)lwe_output_indexes,
                        (const uint64_t*)lut_vector, (const uint64_t*)lut_vector_indexes,
                        (const uint64_t*)lwe_array_in, (const uint64_t*)lwe_input_indexes, f, lwe_dimension,
@@ -855,9 +856,7 @@ void cuda_keyswitch_lwe_ciphertext_vector_64(void* stream, uint32_t gpu_index, v
 // ----------------------------------------------------------------------------------------
 // bit extraction (WoP-PBS stage 1), reference names (concrete-cuda cuda_bind.rs:494-567)
 // ----------------------------------------------------------------------------------------
-// sizes of the buffers handed out by scratch_cuda_extract_bits_64 (the call itself carries none)
-static std::mutex g_eb_mu;
-static std::unordered_map<const void*, uint64_t> g_eb_scratch;
+static ScratchRegistry g_eb_scratch;  // the buffers handed out by scratch_cuda_extract_bits_64
 
 void scratch_cuda_extract_bits_64(void* stream, uint32_t gpu_index, int8_t** bit_extract_buffer,
                                   uint32_t glwe_dimension, uint32_t lwe_dimension, uint32_t polynomial_size,
@@ -877,26 +876,11 @@ void scratch_cuda_extract_bits_64(void* stream, uint32_t gpu_index, int8_t** bit
   const uint64_t bytes = concrete_hip_extract_bits_scratch_bytes(glwe_dimension * polynomial_size, lwe_dimension,
                                                                  glwe_dimension, polynomial_size, number_of_inputs, 63);
   if (!allocate_gpu_memory || bytes == 0) return;  // NULL: cuda_extract_bits_64 takes pool scratch
-  set_device(gpu_index);
-  keep_pool_memory();
-  void* p = nullptr;
-  CHIP_CHECK(hipMallocAsync(&p, bytes, (hipStream_t)stream));
-  {
-    std::lock_guard<std::mutex> g(g_eb_mu);
-    g_eb_scratch[p] = bytes;
-  }
-  *bit_extract_buffer = (int8_t*)p;
+  *bit_extract_buffer = g_eb_scratch.allocate(gpu_index, bytes, stream);
 }
 
 void cleanup_cuda_extract_bits(void* stream, uint32_t gpu_index, int8_t** bit_extract_buffer) {
-  if (!bit_extract_buffer || !*bit_extract_buffer) return;
-  set_device(gpu_index);
-  {
-    std::lock_guard<std::mutex> g(g_eb_mu);
-    g_eb_scratch.erase(*bit_extract_buffer);
-  }
-  CHIP_CHECK(hipFreeAsync(*bit_extract_buffer, (hipStream_t)stream));
-  *bit_extract_buffer = nullptr;
+  g_eb_scratch.release(gpu_index, bit_extract_buffer, stream);
 }
 
 void cuda_extract_bits_64(void* stream, uint32_t gpu_index, void* list_lwe_array_out, const void* lwe_array_in,
@@ -908,33 +892,11 @@ void cuda_extract_bits_64(void* stream, uint32_t gpu_index, void* list_lwe_array
   (void)max_shared_memory;
   // a `dest` of cuda_convert_lwe_programmable_bootstrap_key_64 stands for its registered Fourier key;
   // any other pointer is a caller-owned Fourier key
-  const void* f = fourier_bsk;
-  {
-    std::lock_guard<std::mutex> g(g_keys_mu);
-    auto it = g_keys.find(fourier_bsk);
-    if (it != g_keys.end()) {
-      const KeyEntry& e = it->second;
-      if (e.n != lwe_dimension_out || e.k != glwe_dimension || e.level != level_count_bsk || e.N != polynomial_size ||
-          e.gpu != gpu_index) {
-        set_error("bootstrapping key converted for n=%u k=%u level=%u N=%u on gpu %u, called with n=%u k=%u "
-                  "level=%u N=%u on gpu %u",
-                  e.n, e.k, e.level, e.N, e.gpu, lwe_dimension_out, glwe_dimension, level_count_bsk, polynomial_size,
-                  gpu_index);
-        die("cuda_extract_bits_64");
-      }
-      f = e.fourier;
-    }
-  }
-  uint64_t bytes = 0;
-  if (bit_extract_buffer) {
-    std::lock_guard<std::mutex> g(g_eb_mu);
-    auto it = g_eb_scratch.find(bit_extract_buffer);
-    if (it == g_eb_scratch.end()) {
-      set_error("buffer %p does not come from scratch_cuda_extract_bits_64", (void*)bit_extract_buffer);
-      die("cuda_extract_bits_64");
-    }
-    bytes = it->second;
-  }
+  const void* f = registered_key("cuda_extract_bits_64", fourier_bsk, gpu_index, lwe_dimension_out, glwe_dimension,
+                                 level_count_bsk, polynomial_size);
+  if (!f) f = fourier_bsk;
+  const uint64_t bytes =
+      g_eb_scratch.size_of("cuda_extract_bits_64", "scratch_cuda_extract_bits_64", bit_extract_buffer);
   const std::vector<uint32_t> nb(number_of_samples, number_of_bits), dl(number_of_samples, delta_log);
   if (concrete_hip_extract_bits(stream, gpu_index, (uint64_t*)list_lwe_array_out, (const uint64_t*)lwe_array_in, f,
                                 (const uint64_t*)ksk, nb.data(), dl.data(), nullptr, lwe_dimension_in,

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "companion.hpp"
 #include "fft512.hpp"
 #include "keycheck.hpp"
 #include "pbs.hpp"
@@ -31,8 +32,6 @@
 #pragma clang fp contract(off)
 
 namespace chip {
-
-void keep_pool_memory();  // abi.hip: the default pool never releases (see there)
 
 struct dd {
   double hi, lo;
@@ -86,6 +85,30 @@ __device__ __forceinline__ double limb_value(uint64_t rem, uint32_t limb) {
   return (double)lv;
 }
 
+constexpr int ilog2(int x) { return x <= 1 ? 0 : 1 + ilog2(x / 2); }
+
+// The next digit of a mixed-radix block index, least significant first: t % radix, and t /= radix.
+__device__ __forceinline__ uint32_t next_digit(uint64_t& t, uint32_t radix) {
+  const uint32_t d = (uint32_t)(t % radix);
+  t /= radix;
+  return d;
+}
+
+// The M points the transform starts from: limb `limb` of the polynomial whose coefficient j is
+// g[step * j], folded and twisted, z_j = (a_j + i a_{j+M}) * zeta^j, stored at the bit-reversed position
+// for the DIT passes.
+template <int M, int LIMBS>
+__device__ __forceinline__ void load_twisted(ddc* buf, const uint64_t* __restrict__ g, int step, uint32_t limb,
+                                             const ddc* __restrict__ zeta_t) {
+  for (int j = threadIdx.x; j < M; j += blockDim.x) {
+    ddc z{dd_from(limb_value<LIMBS>(g[step * j], limb)), dd_from(limb_value<LIMBS>(g[step * (j + M)], limb))};
+    z = ddc_mul(z, zeta_t[j]);
+    const int r = (int)(__builtin_bitreverse32((uint32_t)j) >> (32 - ilog2(M)));
+    buf[r] = z;
+  }
+  __syncthreads();
+}
+
 // In-LDS radix-2 DIT over buf (bit-reversed input, natural output, forward sign)
 template <int M>
 __device__ __forceinline__ void dd_fft(ddc* buf, const ddc* __restrict__ tw_t) {
@@ -103,61 +126,49 @@ __device__ __forceinline__ void dd_fft(ddc* buf, const ddc* __restrict__ tw_t) {
   }
 }
 
+// The stored f64 value of a double-double one: rn((hi + lo) * scale) per component.
+__device__ __forceinline__ cplx dd_round(ddc x, double scale) {
+  return {(x.re.hi + x.re.lo) * scale, (x.im.hi + x.im.lo) * scale};
+}
+
 // dd_fft, then the scatter into the PBS kernels' register layout: element e = (slot, lane) holds
-// frequency fft512_freq(lane, slot), scaled 1/M, stored at dst(e).
+// frequency fft512_freq(lane, slot), scaled, stored at dst(e).
 template <int M, class Dst>
-__device__ __forceinline__ void dd_fft_scatter(ddc* buf, const ddc* __restrict__ tw_t, Dst dst,
+__device__ __forceinline__ void dd_fft_scatter(ddc* buf, const ddc* __restrict__ tw_t, double scale, Dst dst,
                                                unsigned long long* smax) {
   dd_fft<M>(buf, tw_t);
-  const double scale = 1.0 / (double)M;
   double m2 = 0.0;
   for (int e = threadIdx.x; e < M; e += blockDim.x) {
-    const int lane = e & 63, slot = e >> 6;
-    const int f = fft512_freq(lane, slot);
-    const ddc x = buf[f];
-    const cplx y = {(x.re.hi + x.re.lo) * scale, (x.im.hi + x.im.lo) * scale};
+    const cplx y = dd_round(buf[fft512_freq(e & 63, e >> 6)], scale);
     *dst(e) = y;
     m2 = fmax(m2, spec_mag2(y.re, y.im));
   }
   spec_max_commit(smax, m2);
 }
 
+// N = 1024, k = 1, l <= 3 (pbs.hip).  Block = (poly, limb), poly the index in the standard layout.
 // tables: zeta[j] = exp(i pi j / N) for j < N/2 ; tw[t] = exp(-2 pi i t / (N/2)) for t < N/4
-template <int N, int K, int L, int LIMBS>
+template <int LIMBS>
 __global__ void __launch_bounds__(256) convert_bsk_kernel(cplx* __restrict__ dest, const uint64_t* __restrict__ src,
                                                          const ddc* __restrict__ zeta_t, const ddc* __restrict__ tw_t,
-                                                         uint32_t n, unsigned long long* smax) {
-  constexpr int M = N / 2, LOGM = (M == 512 ? 9 : (M == 1024 ? 10 : (M == 256 ? 8 : 11)));
-  constexpr int K1 = K + 1;
+                                                         uint32_t level, unsigned long long* smax) {
+  constexpr int M = 512, N = 1024;
   __shared__ ddc buf[M];
-  // block = (poly, limb); poly index in the standard layout
-  const uint64_t blk = blockIdx.x;
-  const uint32_t limb = (uint32_t)(blk % LIMBS);
-  const uint64_t poly = blk / LIMBS;
-  const uint32_t col = (uint32_t)(poly % K1);
-  const uint32_t row = (uint32_t)((poly / K1) % K1);
-  const uint32_t v = (uint32_t)((poly / (K1 * K1)) % L);
-  const uint64_t i = poly / ((uint64_t)K1 * K1 * L);
-  const uint64_t* g = src + poly * N;
-
-  for (int j = threadIdx.x; j < M; j += blockDim.x) {
-    // z_j = (a + i b) * zeta^j ; store at bit-reversed position for the DIT passes
-    ddc z{dd_from(limb_value<LIMBS>(g[j], limb)), dd_from(limb_value<LIMBS>(g[j + M], limb))};
-    z = ddc_mul(z, zeta_t[j]);
-    const int r = (int)(__builtin_bitreverse32((uint32_t)j) >> (32 - LOGM));
-    buf[r] = z;
-  }
-  __syncthreads();
+  uint64_t t = blockIdx.x;
+  const uint32_t limb = next_digit(t, LIMBS);
+  const uint64_t poly = t;
+  const uint32_t col = next_digit(t, 2), row = next_digit(t, 2), v = next_digit(t, level);
+  const uint64_t i = t;
+  load_twisted<M, LIMBS>(buf, src + poly * N, 1, limb, zeta_t);
   // layout [n][limb][co][ro][q][slot][lane] (pbs.hip): slots 0..3 of group (limb, co, ro) hold
-  // column co / row ro, slots 4..7 hold column 1 - co / row 1 - ro (K = 1), so each wave of a
-  // pair reads "own" and "other" spectra at fixed positions
-  static_assert(K1 == 2, "own/other key layout assumes k = 1");
-  const uint32_t q = (uint32_t)(L - 1) - v;
-  cplx* base = dest + i * (uint64_t)(LIMBS * 4 * L * M);  // per GGSW: limbs x co x ro x levels
-  dd_fft_scatter<M>(buf, tw_t, [&](int e) {
+  // column co / row ro, slots 4..7 hold column 1 - co / row 1 - ro, so each wave of a pair reads
+  // "own" and "other" spectra at fixed positions (the own/other layout assumes k = 1)
+  const uint32_t q = level - 1 - v;
+  cplx* base = dest + i * (uint64_t)(LIMBS * 4 * level * M);  // per GGSW: limbs x co x ro x levels
+  dd_fft_scatter<M>(buf, tw_t, 1.0 / (double)M, [&](int e) {
     const int slot = e >> 6, lane = e & 63;
     const uint32_t co = slot < 4 ? col : 1u - col, ro = slot < 4 ? row : 1u - row;
-    return base + (((uint64_t)(limb * 2 + co) * 2 + ro) * L + q) * M + slot * 64 + lane;
+    return base + (((uint64_t)(limb * 2 + co) * 2 + ro) * level + q) * M + slot * 64 + lane;
   }, smax);
 }
 
@@ -173,24 +184,17 @@ __global__ void __launch_bounds__(256) convert_bsk2048_kernel(cplx* __restrict__
                                                              const ddc* __restrict__ tw_t,
                                                              const ddc* __restrict__ sroot_t, uint32_t level,
                                                              unsigned long long* smax) {
-  constexpr int M = 512, LOGM = 9;
+  constexpr int M = 512;
   __shared__ ddc buf[2][M];
   const uint64_t blk = blockIdx.x;
-  const uint32_t row = (uint32_t)(blk & 1);
-  const uint32_t q = (uint32_t)((blk >> 1) % level);
-  const uint32_t col = (uint32_t)((blk >> 1) / level & 1);
-  const uint32_t limb = (uint32_t)(((blk >> 1) / level >> 1) % LIMBS);
-  const uint64_t i = ((blk >> 1) / level >> 1) / LIMBS;
+  uint64_t t = blk;
+  const uint32_t row = next_digit(t, 2), q = next_digit(t, level), col = next_digit(t, 2);
+  const uint32_t limb = next_digit(t, LIMBS);
+  const uint64_t i = t;
   const uint32_t v = level - 1 - q;
   const uint64_t* g = src + ((i * level + v) * 4 + row * 2 + col) * 2048;  // [n][l][row][col][N]
-  for (int e = threadIdx.x; e < 2 * M; e += blockDim.x) {
-    const int par = e / M, j = e % M;
-    ddc z{dd_from(limb_value<LIMBS>(g[2 * j + par], limb)), dd_from(limb_value<LIMBS>(g[2 * (j + M) + par], limb))};
-    z = ddc_mul(z, zeta_t[j]);
-    const int r = (int)(__builtin_bitreverse32((uint32_t)j) >> (32 - LOGM));
-    buf[par][r] = z;
-  }
-  __syncthreads();
+  // as a loop: written out as two calls the kernel takes 65 VGPRs, above every kernel this file had (63)
+  for (int par = 0; par < 2; ++par) load_twisted<M, LIMBS>(buf[par], g + par, 2, limb, zeta_t);
   dd_fft<M>(buf[0], tw_t);
   dd_fft<M>(buf[1], tw_t);
   const double scale = 0.5 / (double)M;
@@ -202,8 +206,7 @@ __global__ void __launch_bounds__(256) convert_bsk2048_kernel(cplx* __restrict__
     const ddc ge = buf[0][f];
     const ddc kp{dd_add(ge.re, so.re), dd_add(ge.im, so.im)};
     const ddc km{dd_add(ge.re, dd_neg(so.re)), dd_add(ge.im, dd_neg(so.im))};
-    const cplx yp = {(kp.re.hi + kp.re.lo) * scale, (kp.im.hi + kp.im.lo) * scale};
-    const cplx ym = {(km.re.hi + km.re.lo) * scale, (km.im.hi + km.im.lo) * scale};
+    const cplx yp = dd_round(kp, scale), ym = dd_round(km, scale);
     base[e] = yp;
     base[M + e] = ym;
     m2 = fmax(m2, fmax(spec_mag2(yp.re, yp.im), spec_mag2(ym.re, ym.im)));
@@ -211,41 +214,31 @@ __global__ void __launch_bounds__(256) convert_bsk2048_kernel(cplx* __restrict__
   spec_max_commit(smax, m2);
 }
 
-// N = 1024, k = 2 (pbs1024k2.hip; l >= K2_MANY_MIN: level-major, [n][q][limb][col][row][512]).  Block = (i, limb, col, q, row), in the order of the
-// output layout [n][limb][col][q][row][512]: limb `limb` of key polynomial (row, col) of level
-// v = l - 1 - q (q in digit order), folded, twisted and transformed like the k = 1 key.
+// N = 1024, k = 2 (pbs1024k2.hip).  Block = (i, limb, col, q, row), in the order of the output layout
+// [n][limb][col][q][row][512] (l >= K2_MANY_MIN: level-major, [n][q][limb][col][row][512]): limb `limb`
+// of key polynomial (row, col) of level v = l - 1 - q (q in digit order), folded, twisted and
+// transformed like the k = 1 key.
 __global__ void __launch_bounds__(256) convert_bsk1024k2_kernel(cplx* __restrict__ dest,
                                                                const uint64_t* __restrict__ src,
                                                                const ddc* __restrict__ zeta_t,
                                                                const ddc* __restrict__ tw_t, uint32_t level,
                                                                unsigned long long* smax) {
-  constexpr int M = 512, LOGM = 9, N = 1024;
+  constexpr int M = 512, N = 1024;
   __shared__ ddc buf[M];
   const uint64_t blk = blockIdx.x;
-  const uint32_t row = (uint32_t)(blk % 3);
+  uint64_t t = blk;
+  const uint32_t row = next_digit(t, 3);
   uint32_t q, col, limb;
-  uint64_t i;
   if (level >= K2_MANY_MIN) {  // level-major: [n][q][limb][col][row]
-    col = (uint32_t)((blk / 3) % 3);
-    limb = (uint32_t)((blk / 9) % K2_LIMBS);
-    q = (uint32_t)((blk / (9 * K2_LIMBS)) % level);
-    i = blk / (9 * K2_LIMBS * level);
+    col = next_digit(t, 3), limb = next_digit(t, K2_LIMBS), q = next_digit(t, level);
   } else {
-    q = (uint32_t)((blk / 3) % level);
-    col = (uint32_t)((blk / (3 * level)) % 3);
-    limb = (uint32_t)((blk / (9 * level)) % K2_LIMBS);
-    i = blk / (9 * level * K2_LIMBS);
+    q = next_digit(t, level), col = next_digit(t, 3), limb = next_digit(t, K2_LIMBS);
   }
+  const uint64_t i = t;
   const uint32_t v = level - 1 - q;
   const uint64_t* g = src + (((i * level + v) * 3 + row) * 3 + col) * N;  // [n][l][row][col][N]
-  for (int j = threadIdx.x; j < M; j += blockDim.x) {
-    ddc z{dd_from(limb_value<K2_LIMBS>(g[j], limb)), dd_from(limb_value<K2_LIMBS>(g[j + M], limb))};
-    z = ddc_mul(z, zeta_t[j]);
-    const int r = (int)(__builtin_bitreverse32((uint32_t)j) >> (32 - LOGM));
-    buf[r] = z;
-  }
-  __syncthreads();
-  dd_fft_scatter<M>(buf, tw_t, [&](int e) { return dest + blk * M + e; }, smax);
+  load_twisted<M, K2_LIMBS>(buf, g, 1, limb, zeta_t);
+  dd_fft_scatter<M>(buf, tw_t, 1.0 / (double)M, [&](int e) { return dest + blk * M + e; }, smax);
 }
 
 // N = 512, k = 3 / N = 256, k = 5, 6, l <= 3 (pbs_small.hip) and N = 512, k = 4, l = 1, 3 .. 5
@@ -261,59 +254,32 @@ __global__ void __launch_bounds__(256) convert_bsk_small_kernel(cplx* __restrict
                                                                const ddc* __restrict__ zeta_t,
                                                                const ddc* __restrict__ tw_t, uint32_t level,
                                                                unsigned long long* smax) {
-  constexpr int M = N / 2, LOGM = N == 512 ? 8 : 7, P = 1024 / N;
+  constexpr int M = N / 2, P = 1024 / N;
   constexpr int GC = sm_gc(N, K1), NCG = K1 / GC;
   __shared__ ddc buf[M];
   const uint64_t blk = blockIdx.x;
   uint64_t t = blk;
-  const uint32_t row = (uint32_t)(t % K1);
-  t /= K1;
+  const uint32_t row = next_digit(t, K1);
   uint32_t c2, q, cg, limb;
-  uint64_t i;
   if (N == 512 && K1 == 5 && level >= K4_MANY_MIN) {  // level-major: [n][q][limb][col][row] (GC = 1)
-    c2 = 0;
-    cg = (uint32_t)(t % K1);
-    t /= K1;
-    limb = (uint32_t)(t % LIMBS);
-    t /= LIMBS;
-    q = (uint32_t)(t % level);
-    i = t / level;
+    c2 = 0, cg = next_digit(t, K1), limb = next_digit(t, LIMBS), q = next_digit(t, level);
   } else {
-    c2 = (uint32_t)(t % GC);
-    t /= GC;
-    q = (uint32_t)(t % level);
-    t /= level;
-    cg = (uint32_t)(t % NCG);
-    t /= NCG;
-    limb = (uint32_t)(t % LIMBS);
-    i = t / LIMBS;
+    c2 = next_digit(t, GC), q = next_digit(t, level), cg = next_digit(t, NCG), limb = next_digit(t, LIMBS);
   }
+  const uint64_t i = t;
   const uint32_t col = cg * GC + c2, v = level - 1 - q;
   const uint64_t* g = src + (((i * level + v) * K1 + row) * K1 + col) * N;  // [n][l][row][col][N]
-  for (int j = threadIdx.x; j < M; j += blockDim.x) {
-    ddc z{dd_from(limb_value<LIMBS>(g[j], limb)), dd_from(limb_value<LIMBS>(g[j + M], limb))};
-    z = ddc_mul(z, zeta_t[j]);
-    const int r = (int)(__builtin_bitreverse32((uint32_t)j) >> (32 - LOGM));
-    buf[r] = z;
-  }
-  __syncthreads();
-  dd_fft<M>(buf, tw_t);
-  const double scale = 1.0 / (512.0 * P);
-  double m2 = 0.0;
-  for (int e = threadIdx.x; e < M; e += blockDim.x) {
-    const ddc x = buf[fft512_freq(e & 63, e >> 6)];
-    const cplx y = {(x.re.hi + x.re.lo) * scale, (x.im.hi + x.im.lo) * scale};
-    dest[blk * M + e] = y;
-    m2 = fmax(m2, spec_mag2(y.re, y.im));
-  }
-  spec_max_commit(smax, m2);
+  load_twisted<M, LIMBS>(buf, g, 1, limb, zeta_t);
+  dd_fft_scatter<M>(buf, tw_t, 1.0 / (512.0 * P), [&](int e) { return dest + blk * M + e; }, smax);
 }
 
-template <int N, int K, int L, int LIMBS>
-static int launch_convert(const ConvertArgs& a, const ddc* zeta, const ddc* tw) {
-  const uint64_t blocks = (uint64_t)a.n * L * (K + 1) * (K + 1) * LIMBS;
-  hipLaunchKernelGGL((convert_bsk_kernel<N, K, L, LIMBS>), dim3((uint32_t)blocks), dim3(256), 0, a.stream,
-                     reinterpret_cast<cplx*>(a.dest), a.src_dev, zeta, tw, a.n, a.smax);
+// One workgroup of 256 threads per (polynomial, limb) of the key, on a.stream; `rest`: the kernel's
+// arguments after dest and src.  0, or -1 with the error recorded.
+template <class... P, class... A>
+static int launch_convert(void (*kernel)(P...), const ConvertArgs& a, A... rest) {
+  const uint64_t blocks = (uint64_t)a.n * a.level * (a.k + 1) * (a.k + 1) * a.limbs;
+  hipLaunchKernelGGL(kernel, dim3((uint32_t)blocks), dim3(256), 0, a.stream, reinterpret_cast<cplx*>(a.dest),
+                     a.src_dev, rest...);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     set_error("convert launch failed: %s", hipGetErrorString(e));
@@ -359,75 +325,42 @@ static void make_sroots(std::vector<ddc>& sr) {
   }
 }
 
+// A host table in stream-ordered device memory (freed by the caller after the launch).
+static ddc* upload_table(const std::vector<ddc>& t, hipStream_t s) {
+  ddc* d = nullptr;
+  CHIP_CHECK(hipMallocAsync((void**)&d, t.size() * sizeof(ddc), s));
+  CHIP_CHECK(hipMemcpyAsync(d, t.data(), t.size() * sizeof(ddc), hipMemcpyHostToDevice, s));
+  return d;
+}
+
 int convert_bsk_launch(const ConvertArgs& a) {
-  if (key_format(a.k, a.N, a.level).kind == KeyKind::GENERIC) return convert_bsk_generic_launch(a);
-  const bool n1024 = a.N == 1024 && a.k == 1 && a.limbs == 3 && a.level >= 1 && a.level <= 3;
-  const bool n2048 =
-      a.N == 2048 && a.k == 1 && a.limbs == (uint32_t)PBS2_LIMBS && a.level >= 1 && a.level <= PBS2_MAX_LEVEL;
-  const bool k2 = a.N == 1024 && a.k == 2 && a.limbs == (uint32_t)K2_LIMBS && a.level >= 1 && a.level <= 64;
-  const bool small = pbs_small_shape(a.k, a.N, a.level) && a.limbs == small_limbs(a.k, a.N, a.level);
-  if (!n1024 && !n2048 && !k2 && !small) {
+  const KeyFormat f = key_format(a.k, a.N, a.level);
+  if (f.kind == KeyKind::GENERIC) return convert_bsk_generic_launch(a);
+  if (f.kind == KeyKind::NONE || a.limbs != f.limbs) {
     set_error("unsupported BSK conversion parameters: N=%u k=%u level=%u limbs=%u", a.N, a.k, a.level, a.limbs);
     return -2;
   }
-  std::vector<ddc> zeta, tw;
-  make_tables(small ? a.N : 1024, zeta, tw);  // the others transform N = 1024 negacyclic polynomials
-  ddc *dz = nullptr, *dt = nullptr;
+  std::vector<ddc> zeta, tw, sr;
+  make_tables(f.kind == KeyKind::SMALL ? a.N : 1024, zeta, tw);  // the others transform N = 1024 negacyclic polynomials
   keep_pool_memory();
-  CHIP_CHECK(hipMallocAsync((void**)&dz, zeta.size() * sizeof(ddc), a.stream));
-  CHIP_CHECK(hipMallocAsync((void**)&dt, tw.size() * sizeof(ddc), a.stream));
-  CHIP_CHECK(hipMemcpyAsync(dz, zeta.data(), zeta.size() * sizeof(ddc), hipMemcpyHostToDevice, a.stream));
-  CHIP_CHECK(hipMemcpyAsync(dt, tw.data(), tw.size() * sizeof(ddc), hipMemcpyHostToDevice, a.stream));
-  int rc = 0;
-  std::vector<ddc> sr;
-  ddc* ds = nullptr;
-  if (n2048) {
-    make_sroots(sr);
-    CHIP_CHECK(hipMallocAsync((void**)&ds, sr.size() * sizeof(ddc), a.stream));
-    CHIP_CHECK(hipMemcpyAsync(ds, sr.data(), sr.size() * sizeof(ddc), hipMemcpyHostToDevice, a.stream));
-    const uint64_t blocks = (uint64_t)a.n * PBS2_LIMBS * 4 * a.level;
-    hipLaunchKernelGGL((convert_bsk2048_kernel<PBS2_LIMBS>), dim3((uint32_t)blocks), dim3(256), 0, a.stream,
-                       reinterpret_cast<cplx*>(a.dest), a.src_dev, dz, dt, ds, a.level, a.smax);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-      set_error("convert launch failed: %s", hipGetErrorString(e));
-      rc = -1;
-    }
-  } else if (small) {
-    const uint64_t blocks = (uint64_t)a.n * a.limbs * (a.k + 1) * (a.k + 1) * a.level;
-    if (a.N == 512 && a.k == 3)
-      hipLaunchKernelGGL((convert_bsk_small_kernel<512, 4>), dim3((uint32_t)blocks), dim3(256), 0, a.stream,
-                         reinterpret_cast<cplx*>(a.dest), a.src_dev, dz, dt, a.level, a.smax);
-    else if (a.N == 512 && a.limbs == K4_L2_LIMBS)
-      hipLaunchKernelGGL((convert_bsk_small_kernel<512, 5, K4_L2_LIMBS>), dim3((uint32_t)blocks), dim3(256), 0,
-                         a.stream, reinterpret_cast<cplx*>(a.dest), a.src_dev, dz, dt, a.level, a.smax);
-    else if (a.N == 512)
-      hipLaunchKernelGGL((convert_bsk_small_kernel<512, 5>), dim3((uint32_t)blocks), dim3(256), 0, a.stream,
-                         reinterpret_cast<cplx*>(a.dest), a.src_dev, dz, dt, a.level, a.smax);
-    else if (a.k == 5)
-      hipLaunchKernelGGL((convert_bsk_small_kernel<256, 6>), dim3((uint32_t)blocks), dim3(256), 0, a.stream,
-                         reinterpret_cast<cplx*>(a.dest), a.src_dev, dz, dt, a.level, a.smax);
-    else
-      hipLaunchKernelGGL((convert_bsk_small_kernel<256, 7>), dim3((uint32_t)blocks), dim3(256), 0, a.stream,
-                         reinterpret_cast<cplx*>(a.dest), a.src_dev, dz, dt, a.level, a.smax);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-      set_error("convert launch failed: %s", hipGetErrorString(e));
-      rc = -1;
-    }
-  } else if (k2) {
-    const uint64_t blocks = (uint64_t)a.n * K2_LIMBS * 9 * a.level;
-    hipLaunchKernelGGL(convert_bsk1024k2_kernel, dim3((uint32_t)blocks), dim3(256), 0, a.stream,
-                       reinterpret_cast<cplx*>(a.dest), a.src_dev, dz, dt, a.level, a.smax);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-      set_error("convert launch failed: %s", hipGetErrorString(e));
-      rc = -1;
-    }
-  } else switch (a.level) {
-    case 1: rc = launch_convert<1024, 1, 1, 3>(a, dz, dt); break;
-    case 2: rc = launch_convert<1024, 1, 2, 3>(a, dz, dt); break;
-    default: rc = launch_convert<1024, 1, 3, 3>(a, dz, dt); break;
+  ddc *dz = upload_table(zeta, a.stream), *dt = upload_table(tw, a.stream), *ds = nullptr;
+  int rc;
+  switch (f.kind) {
+    case KeyKind::N2048:
+      make_sroots(sr);
+      ds = upload_table(sr, a.stream);
+      rc = launch_convert(convert_bsk2048_kernel<PBS2_LIMBS>, a, dz, dt, ds, a.level, a.smax);
+      break;
+    case KeyKind::K2N1024: rc = launch_convert(convert_bsk1024k2_kernel, a, dz, dt, a.level, a.smax); break;
+    case KeyKind::SMALL:
+      rc = launch_convert(a.N == 512 && a.k == 3         ? convert_bsk_small_kernel<512, 4>
+                          : a.limbs == K4_L2_LIMBS       ? convert_bsk_small_kernel<512, 5, K4_L2_LIMBS>
+                          : a.N == 512                   ? convert_bsk_small_kernel<512, 5>
+                          : a.k == 5                     ? convert_bsk_small_kernel<256, 6>
+                                                         : convert_bsk_small_kernel<256, 7>,
+                          a, dz, dt, a.level, a.smax);
+      break;
+    default: rc = launch_convert(convert_bsk_kernel<3>, a, dz, dt, a.level, a.smax); break;  // N1024
   }
   // the host tables must outlive the async copies: synchronise before they go out of scope
   CHIP_CHECK(hipStreamSynchronize(a.stream));

@@ -27,8 +27,6 @@
 
 namespace chip {
 
-void keep_pool_memory();  // abi.hip
-
 constexpr uint32_t EB_MAX_BITS = 63;  // dl >= 1 and dl + nb <= 64
 constexpr uint32_t EB_MAX_ACCS = 63;  // accumulators differ by e = dl - 1 + t only, e in 0 .. 62
 
@@ -267,11 +265,7 @@ int concrete_hip_extract_bits(void* stream, uint32_t gpu_index, uint64_t* lwe_ar
   const uint64_t W = (uint64_t)lwe_dimension_in + 1, w = (uint64_t)lwe_dimension_out + 1;
   const uint64_t G = ((uint64_t)glwe_dimension + 1) * polynomial_size;
   const EbLayout lay = eb_layout(B, W, w, G, max_bits);
-  if (scratch && (scratch_bytes < lay.bytes || ((uintptr_t)scratch & 15))) {
-    set_error("extract_bits: scratch of %llu bytes at %p; %llu bytes, 16-byte aligned, are needed",
-              (unsigned long long)scratch_bytes, scratch, (unsigned long long)lay.bytes);
-    return -3;
-  }
+  if (const int rc = scratch_refused("extract_bits", scratch, scratch_bytes, lay.bytes)) return rc;
 
   // ---- schedule: rows by decreasing nb; active[t] = rows with nb > t (a prefix of that order) ----
   std::vector<uint32_t> order(B);
@@ -326,11 +320,8 @@ int concrete_hip_extract_bits(void* stream, uint32_t gpu_index, uint64_t* lwe_ar
   }
   for (uint32_t i = 0; i < slots; ++i) h_exps[i] = exps[i];
 
-  char* base = (char*)scratch;
-  if (!base) {
-    keep_pool_memory();
-    CHIP_CHECK(hipMallocAsync((void**)&base, lay.bytes, s));
-  }
+  const CallScratch own(scratch, lay.bytes, s);
+  char* base = own.base;
   uint64_t* d_copy = (uint64_t*)(base + lay.copy);
   uint64_t* d_ks_in = (uint64_t*)(base + lay.ks_in);
   uint64_t* d_pbs_out = (uint64_t*)(base + lay.pbs_out);
@@ -373,7 +364,6 @@ int concrete_hip_extract_bits(void* stream, uint32_t gpu_index, uint64_t* lwe_ar
     ko += A, lo += P;
   }
   const hipError_t e = hipGetLastError();
-  if (!scratch) CHIP_CHECK(hipFreeAsync(base, s));
   if (rc == 0 && e != hipSuccess) {
     set_error("extract_bits launch failed: %s", hipGetErrorString(e));
     rc = -1;

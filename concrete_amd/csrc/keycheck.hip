@@ -31,8 +31,6 @@
 
 namespace chip {
 
-void keep_pool_memory();  // abi.hip
-
 // scale of the stored spectra (the kernels' inverse normalisation folded into the key)
 static double stored_scale(const KeyFormat& f, uint32_t N) {
   switch (f.kind) {

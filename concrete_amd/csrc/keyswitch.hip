@@ -16,14 +16,11 @@
 #include <vector>
 
 #include "common.hpp"
+#include "companion.hpp"
 #include "kernel_util.hpp"
 #include "pbs.hpp"
 
 namespace chip {
-
-// abi.hip: raise the device's default memory-pool release threshold once (released and re-reserved
-// pool memory reads stale data on this stack; pooled scratch also saves ~0.1 ms per call at cfg2).
-void keep_pool_memory();
 
 constexpr int KS_TILE = 8;
 constexpr int KS_THREADS = 256;
@@ -451,15 +448,12 @@ int release_key_bytes(const void* p, hipStream_t s, bool untrack) {
         ++it;
       }
   }
-  int prev = 0;
-  if (!gone.empty()) CHIP_CHECK(hipGetDevice(&prev));
   for (KeyBytes& e : gone) {
-    CHIP_CHECK(hipSetDevice(e.dev));
+    DeviceScope dev(e.dev);
     if (s) CHIP_CHECK(hipFreeAsync(e.bt, s));
     else CHIP_CHECK(hipFree(e.bt));
     CHIP_CHECK(hipEventDestroy(e.built));
   }
-  if (!gone.empty()) CHIP_CHECK(hipSetDevice(prev));
   return (int)gone.size();
 }
 

@@ -465,7 +465,7 @@ int concrete_hip_keyset_add_bsk(concrete_hip_keyset* ks, uint32_t bsk_index, con
       set_error("keyset_add_bsk: index %u already resident", bsk_index);
       return -3;
     }
-  const uint64_t len = (uint64_t)input_lwe_dim * level * ((uint64_t)glwe_dim + 1) * ((uint64_t)glwe_dim + 1) * poly_size;
+  const uint64_t len = std_bsk_bytes(input_lwe_dim, glwe_dim, level, poly_size) / 8;
   e->host.assign(bsk, bsk + len);
   e->n = input_lwe_dim, e->k = glwe_dim, e->level = level, e->base_log = base_log, e->N = poly_size;
   return 0;
@@ -527,15 +527,12 @@ void concrete_hip_keyset_set_timing(concrete_hip_keyset* ks, int enable) {
   if (!enable) return;
   // one base event per device, in the past of every later call: slices of different calls (and
   // streams) share the time axis
-  int prev = 0;
-  CHIP_CHECK(hipGetDevice(&prev));
   for (uint32_t d : devs) {
-    CHIP_CHECK(hipSetDevice((int)d));
+    DeviceScope dev((int)d);
     if (!ks->timing_base[d]) CHIP_CHECK(hipEventCreate(&ks->timing_base[d]));
     CHIP_CHECK(hipEventRecord(ks->timing_base[d], nullptr));
     CHIP_CHECK(hipEventSynchronize(ks->timing_base[d]));
   }
-  CHIP_CHECK(hipSetDevice(prev));
   ks->timing = true;
 }
 

@@ -19,8 +19,6 @@
 #include "../../include/concrete_hip.h"
 
 #include <algorithm>
-#include <mutex>
-#include <unordered_map>
 
 #include "common.hpp"
 #include "companion.hpp"
@@ -28,8 +26,6 @@
 #include "vertical_packing.hpp"
 
 namespace chip {
-
-void keep_pool_memory();  // abi.hip
 
 constexpr uint32_t VP_MAX_R = 24;
 
@@ -116,24 +112,12 @@ static int vp_run(void* stream, uint32_t gpu_index, uint64_t* lwe_array_out, uin
     set_error("vertical_packing: r=%u mbr_size=%u tau=%u num_lookups=%u overflow the call's sizes", r, m, tau, lookups);
     return -3;
   }
-  if (scratch && (scratch_bytes < lay.bytes || ((uintptr_t)scratch & 15))) {
-    set_error("vertical_packing: scratch of %llu bytes at %p; %llu bytes, 16-byte aligned, are needed",
-              (unsigned long long)scratch_bytes, scratch, (unsigned long long)lay.bytes);
-    return -3;
-  }
+  if (const int rc = scratch_refused("vertical_packing", scratch, scratch_bytes, lay.bytes)) return rc;
 
   CHIP_CHECK(hipSetDevice((int)gpu_index));
   hipStream_t s = (hipStream_t)stream;
-  char* base = (char*)scratch;
-  if (!base) {
-    keep_pool_memory();
-    CHIP_CHECK(hipMallocAsync((void**)&base, lay.bytes, s));
-  }
-  // every return below goes through done(); a failed CHIP_CHECK does not return at all (hip_fatal aborts)
-  auto done = [&](int rc) {
-    if (!scratch) CHIP_CHECK(hipFreeAsync(base, s));
-    return rc;
-  };
+  const CallScratch own(scratch, lay.bytes, s);
+  char* base = own.base;
 
   // ---- the GGSWs: conversion and the per-key gate (the call's one host synchronisation) ----
   void* keys = base + lay.keys;
@@ -149,7 +133,7 @@ static int vp_run(void* stream, uint32_t gpu_index, uint64_t* lwe_array_out, uin
     if (ggsw_spectrum_max && maxG >= 0.0) *ggsw_spectrum_max = maxG;
     if (rc == 0) rc = key_bound_check(keys, KeyKind::GENERIC, k, N, level, base_log);
     key_spectrum_forget(keys);  // the record was this call's: the scratch address will hold other keys
-    if (rc != 0) return done(rc);
+    if (rc != 0) return rc;
   } else if (ggsw_spectrum_max) {
     *ggsw_spectrum_max = 0.0;
   }
@@ -193,62 +177,28 @@ static int vp_run(void* stream, uint32_t gpu_index, uint64_t* lwe_array_out, uin
     std::swap(cur, other);
   }
   if (rc == 0 && lwe_array_out) rc = vp_extract_launch(s, lwe_array_out, cur, outs, k, N);
-  return done(rc);
+  return rc;
 }
 
-[[noreturn]] static void vp_die(const char* what) {
-  fprintf(stderr, "concrete-hip: %s: %s\n", what, last_error());
-  abort();
-}
-
-// sizes of the buffers handed out by the two scratch calls (the calls that use them carry none)
-static std::mutex g_vp_mu;
-static std::unordered_map<const void*, uint64_t> g_vp_scratch;
+static ScratchRegistry g_vp_scratch;  // the buffers handed out by the two scratch calls
 
 static void vp_scratch(const char* what, void* stream, uint32_t gpu_index, int8_t** buffer, uint32_t k, uint32_t N,
                        uint32_t level, uint32_t r, uint32_t m, uint32_t tau, bool allocate) {
   if (!buffer) {
     set_error("null buffer pointer");
-    vp_die(what);
+    die(what);
   }
   *buffer = nullptr;
   const uint64_t bytes = concrete_hip_vertical_packing_scratch_bytes(k, N, level, r, m, tau, 1);
   if (bytes == 0) {
     set_error("scratch: unsupported parameters k=%u N=%u level=%u r=%u mbr_size=%u tau=%u", k, N, level, r, m, tau);
-    vp_die(what);
+    die(what);
   }
-  if (!allocate) return;  // NULL: the call takes pool scratch
-  CHIP_CHECK(hipSetDevice((int)gpu_index));
-  keep_pool_memory();
-  void* p = nullptr;
-  CHIP_CHECK(hipMallocAsync(&p, bytes, (hipStream_t)stream));
-  {
-    std::lock_guard<std::mutex> g(g_vp_mu);
-    g_vp_scratch[p] = bytes;
-  }
-  *buffer = (int8_t*)p;
-}
-
-static void vp_cleanup(void* stream, uint32_t gpu_index, int8_t** buffer) {
-  if (!buffer || !*buffer) return;
-  CHIP_CHECK(hipSetDevice((int)gpu_index));
-  {
-    std::lock_guard<std::mutex> g(g_vp_mu);
-    g_vp_scratch.erase(*buffer);
-  }
-  CHIP_CHECK(hipFreeAsync(*buffer, (hipStream_t)stream));
-  *buffer = nullptr;
+  if (allocate) *buffer = g_vp_scratch.allocate(gpu_index, bytes, stream);  // else NULL: the call takes pool scratch
 }
 
 static uint64_t vp_scratch_size(const char* what, const int8_t* buffer) {
-  if (!buffer) return 0;
-  std::lock_guard<std::mutex> g(g_vp_mu);
-  auto it = g_vp_scratch.find(buffer);
-  if (it == g_vp_scratch.end()) {
-    set_error("buffer %p does not come from this call's scratch function", (const void*)buffer);
-    vp_die(what);
-  }
-  return it->second;
+  return g_vp_scratch.size_of(what, "this call's scratch function", buffer);
 }
 
 }  // namespace chip
@@ -296,16 +246,16 @@ void cuda_cmux_tree_64(void* stream, uint32_t gpu_index, void* glwe_array_out, c
   const uint64_t bytes = vp_scratch_size("cuda_cmux_tree_64", cmux_tree_buffer);
   if (!glwe_array_out) {
     set_error("null output");
-    vp_die("cuda_cmux_tree_64");
+    die("cuda_cmux_tree_64");
   }
   if (vp_run(stream, gpu_index, nullptr, (uint64_t*)glwe_array_out, (const uint64_t*)ggsw_in,
              (const uint64_t*)lut_vector, nullptr, glwe_dimension, polynomial_size, base_log, level_count, r, 0, tau, 1,
              cmux_tree_buffer, bytes, nullptr, nullptr) != 0)
-    vp_die("cuda_cmux_tree_64");
+    die("cuda_cmux_tree_64");
 }
 
 void cleanup_cuda_cmux_tree(void* stream, uint32_t gpu_index, int8_t** cmux_tree_buffer) {
-  vp_cleanup(stream, gpu_index, cmux_tree_buffer);
+  g_vp_scratch.release(gpu_index, cmux_tree_buffer, stream);
 }
 
 void scratch_cuda_blind_rotation_sample_extraction_64(void* stream, uint32_t gpu_index, int8_t** br_se_buffer,
@@ -326,16 +276,16 @@ void cuda_blind_rotate_and_sample_extraction_64(void* stream, uint32_t gpu_index
   const uint64_t bytes = vp_scratch_size(what, br_se_buffer);
   if (!lwe_out || !lut_vector) {
     set_error("null pointer");
-    vp_die(what);
+    die(what);
   }
   if (vp_run(stream, gpu_index, (uint64_t*)lwe_out, nullptr, (const uint64_t*)ggsw_in, nullptr,
              (const uint64_t*)lut_vector, glwe_dimension, polynomial_size, base_log, level_count, 0, mbr_size, tau, 1,
              br_se_buffer, bytes, nullptr, nullptr) != 0)
-    vp_die(what);
+    die(what);
 }
 
 void cleanup_cuda_blind_rotation_sample_extraction(void* stream, uint32_t gpu_index, int8_t** br_se_buffer) {
-  vp_cleanup(stream, gpu_index, br_se_buffer);
+  g_vp_scratch.release(gpu_index, br_se_buffer, stream);
 }
 
 }  // extern "C"

@@ -9,6 +9,8 @@ products on random keys.  Here the key itself is compared, at the smallest shape
 and code path, on keys of uniform random words with planted polynomials (a constant one, all-ones
 words, single coefficients at j = M and j = N - 1) in the corner positions of the layout.
 """
+import ctypes as C
+
 import numpy as np
 import pytest
 
@@ -83,8 +85,9 @@ def _planted_key(n, k, N, l, seed):
     return key, (a, b, c, d)
 
 
-def _convert(env, n, k, N, l, words, general):
-    """The device key (the tensor that holds it).  The conversion refuses (-2)
+def _convert(env, n, k, N, l, words, general, device_source=False):
+    """The device key (the tensor that holds it), from a host source or (device_source) a copy of it on
+    the device, read in place with src_is_device = 1.  The conversion refuses (-2)
     a key whose recorded max|G| leaves no base_log with a certified bound below 1/2 — the planted
     constant polynomial does that to some formats — after storing and recording it: the refusal
     must be exactly that, and the stored key is compared all the same."""
@@ -97,7 +100,9 @@ def _convert(env, n, k, N, l, words, general):
     assert src.size == p.bsk_len
     s = torch.cuda.current_stream().cuda_stream
     fn = L.concrete_hip_convert_bsk_generic if general else L.concrete_hip_convert_bsk
-    rc = fn(s, 0, out.data_ptr(), src.ctypes.data, 0, n, k, l, N)
+    d_src = B.to_device(src, "cuda:0") if device_source else None
+    rc = fn(s, 0, out.data_ptr(), d_src.data_ptr() if device_source else src.ctypes.data, int(device_source), n, k, l,
+            N)
     torch.cuda.synchronize()
     assert rc in (0, -2), rc
     assert (rc == -2) == (not L.concrete_hip_key_error_bound(out.data_ptr(), 1) < 0.5)
@@ -225,3 +230,74 @@ def test_general_shapes_cover_both_limb_kinds():
     limb is then narrower than the others)."""
     bits = [K.generic_limb_bits(k, N, l) for k, N, l in GENERIC_SHAPES]
     assert any(64 % b == 0 for b in bits) and any(64 % b != 0 for b in bits), bits
+
+
+@pytest.mark.parametrize("general", [False, True], ids=["own-format", "general-format"])
+@pytest.mark.parametrize("shape", [(1, 1024, 1), (1, 2048, 1)], ids=lambda s: "k%d-N%d-l%d" % s)
+def test_host_and_device_sources_give_the_same_key(env, shape, general):
+    """Both convert entry points stage a host source and read a device source in place: the stored keys are
+    equal in every byte, and so is the recorded max|G|."""
+    k, N, l = shape
+    n = 2
+    key, _ = _planted_key(n, k, N, l, 9500 + 7 * N + l)
+    L, B = env["L"], env["B"]
+    got = []
+    for device_source in (False, True):
+        fk = _convert(env, n, k, N, l, key, general, device_source)
+        got.append((B.to_host(fk).copy(), L.concrete_hip_key_spectrum_max(fk.data_ptr())))
+    assert got[0][1] > 0.0 and got[0][1] == got[1][1]
+    assert np.array_equal(got[0][0], got[1][0])
+
+
+def _scratch_round_trip(env, scratch, cleanup, use):
+    """scratch(buf, allocate) and cleanup(buf) of one family; use(buf) is the family's own call."""
+    L, torch = env["L"], env["torch"]
+    buf = C.c_void_p(None)
+    scratch(C.byref(buf), False)
+    assert not buf.value  # allocate_gpu_memory = false: NULL, the call takes pool scratch
+    cleanup(C.byref(buf))  # a no-op on NULL
+    scratch(C.byref(buf), True)
+    assert buf.value
+    use(buf)  # accepted between scratch and cleanup (a buffer that is refused aborts the process)
+    torch.cuda.synchronize()
+    cleanup(C.byref(buf))
+    assert not buf.value
+    cleanup(C.byref(buf))  # a second cleanup is a no-op
+    assert not buf.value
+    assert L.concrete_hip_device_status(0) == 0
+
+
+def test_scratch_round_trip_of_both_families(env):
+    """scratch_cuda_* / cleanup_cuda_* of bit extraction and of vertical packing (its two calls), each at
+    the smallest shape its call supports, on all-zero keys and inputs (a zero key passes every gate; the
+    results are checked in tests/test_gpu_extract_bits.py and tests/test_gpu_vertical_packing.py)."""
+    L, torch = env["L"], env["torch"]
+    s = torch.cuda.current_stream().cuda_stream
+    zeros = lambda words: torch.zeros(words, dtype=torch.int64, device="cuda:0")
+
+    # bit extraction: the PBS shape of test_rotation_equals_the_pbs_kernels (k = 1, N = 1024, l = 3, n = 8),
+    # a one-level keyswitch; one row of 2 bits (keyswitch, PBS, keyswitch)
+    k, N, l, logb, n, ksl, ksb, nb, dl = 1, 1024, 3, 8, 8, 1, 1, 2, 62
+    assert L.concrete_hip_extract_bits_supported(k * N, n, k, N, logb, l, ksb, ksl) == 1
+    fk = _convert(env, n, k, N, l, np.zeros(n * l * (k + 1) ** 2 * N, dtype=np.uint64), False)
+    ksk, inp, out = zeros(ksl * k * N * (n + 1)), zeros(k * N + 1), zeros(nb * (n + 1))
+    _scratch_round_trip(
+        env, lambda b, alloc: L.scratch_cuda_extract_bits_64(s, 0, b, k, n, N, l, 1, 0, alloc),
+        lambda b: L.cleanup_cuda_extract_bits(s, 0, b),
+        lambda b: L.cuda_extract_bits_64(s, 0, out.data_ptr(), inp.data_ptr(), b, ksk.data_ptr(), fk.data_ptr(), nb, dl,
+                                         k * N, n, k, N, logb, l, ksb, ksl, 1, 0))
+
+    # vertical packing: k = 1, N = 512 (tests/test_gpu_vertical_packing.py SHAPES); one tree layer, one rotation
+    k, N, l, logb, tau = 1, 512, 2, 10, 1
+    assert L.concrete_hip_vertical_packing_supported(k, N, l, logb) == 1
+    ggsw, luts, glwe, lwe = zeros(l * (k + 1) ** 2 * N), zeros(tau * 2 * N), zeros(tau * (k + 1) * N), zeros(k * N + 1)
+    _scratch_round_trip(
+        env, lambda b, alloc: L.scratch_cuda_cmux_tree_64(s, 0, b, k, N, l, 1, tau, 0, alloc),
+        lambda b: L.cleanup_cuda_cmux_tree(s, 0, b),
+        lambda b: L.cuda_cmux_tree_64(s, 0, glwe.data_ptr(), ggsw.data_ptr(), luts.data_ptr(), b, k, N, logb, l, 1, tau,
+                                      0))
+    _scratch_round_trip(
+        env, lambda b, alloc: L.scratch_cuda_blind_rotation_sample_extraction_64(s, 0, b, k, N, l, 1, tau, 0, alloc),
+        lambda b: L.cleanup_cuda_blind_rotation_sample_extraction(s, 0, b),
+        lambda b: L.cuda_blind_rotate_and_sample_extraction_64(s, 0, lwe.data_ptr(), ggsw.data_ptr(), glwe.data_ptr(),
+                                                               b, 1, tau, k, N, logb, l, 0))
