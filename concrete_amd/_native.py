@@ -56,6 +56,17 @@ SIGNATURES = {
                                             vp, C.POINTER(C.c_double)]),
     "concrete_hip_vertical_packing_scratch_bytes": (u64, [u32, u32, u32, u32, u32, u32, u32]),
     "concrete_hip_vertical_packing_supported": (i32, [u32, u32, u32, u32]),
+    "cuda_fp_keyswitch_lwe_to_glwe_64": (None, [vp, u32, vp, vp, vp, u32, u32, u32, u32, u32, u32, u32]),
+    "scratch_cuda_circuit_bootstrap_64": (None, [vp, u32, C.POINTER(vp), u32, u32, u32, u32, u32, u32, C.c_bool]),
+    "cuda_circuit_bootstrap_64": (None, [vp, u32, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, u32, u32, u32, u32, u32,
+                                         u32, u32, u32]),
+    "cleanup_cuda_circuit_bootstrap": (None, [vp, u32, C.POINTER(vp)]),
+    "concrete_hip_fp_keyswitch": (i32, [vp, u32, vp, vp, vp, u32, u32, u32, u32, u32, u32, u32]),
+    "concrete_hip_circuit_bootstrap": (i32, [vp, u32, vp, vp, vp, vp, u32, u32, u32, u32, u32, u32, u32, u32, u32,
+                                             u32, u32, vp, u64, vp]),
+    "concrete_hip_circuit_bootstrap_scratch_bytes": (u64, [u32, u32, u32, u32, u32]),
+    "concrete_hip_circuit_bootstrap_supported": (i32, [u32, u32, u32, u32, u32, u32, u32, u32]),
+    "concrete_hip_fpksk_size_words": (u64, [u32, u32, u32]),
     "concrete_hip_abi_version": (u32, []),
     "concrete_hip_last_error": (C.c_char_p, []),
     "concrete_hip_pbs_supported": (i32, [u32, u32, u32, u32]),
@@ -89,6 +100,7 @@ SIGNATURES = {
     "concrete_hip_lwe_decrypt": (u64, [vp, vp, u64]),
     "concrete_hip_bsk_generate": (None, [vp, vp, vp, u64, u64, u64, u64, u64, dbl, u64]),
     "concrete_hip_ksk_generate": (None, [vp, vp, vp, u64, u64, u64, u64, dbl, u64]),
+    "concrete_hip_fpksk_generate": (None, [vp, vp, vp, u64, u64, u64, u64, dbl, u64]),
     "concrete_hip_encode_expand_lut": (None, [vp, u64, vp, u64, u32, i32]),
     # Part 4: runtime glue (memref descriptors expanded: allocated, aligned, offset, sizes, strides)
     "concrete_hip_keyset_create": (vp, []),

@@ -424,3 +424,68 @@ def vertical_packing(p: PbsParams, ggsw, luts, r: int, mbr_size: int, num_lookup
         0 if scratch is None else scratch.numel() * scratch.element_size(), _ptr(resid), C.byref(max_g)),
         "concrete_hip_vertical_packing")
     return out, tree_out, max_g.value
+
+
+# ---------------------------------------------------------------------------------------
+# WoP-PBS stage 2: circuit bootstrap and its fp-ks (concrete_hip_circuit_bootstrap)
+# ---------------------------------------------------------------------------------------
+def fpksk_words(k: int, N: int, level: int) -> int:
+    return int(_native.lib().concrete_hip_fpksk_size_words(k, N, level))
+
+
+def fpksk_generate(p: PbsParams, glwe_sk, level: int, base_log: int, seed: int, std: float | None = None) -> np.ndarray:
+    """The list of k + 1 fp-ks keys, (k+1, kN+1, level, (k+1)N) u64, from the flattened GLWE key (the PBS
+    output's LWE key) to the same GLWE key."""
+    sk = np.ascontiguousarray(glwe_sk, dtype=np.uint64)
+    out = np.zeros((p.k + 1, p.big_n + 1, level, p.glwe_size), dtype=np.uint64)
+    assert out.size == fpksk_words(p.k, p.N, level)
+    _native.lib().concrete_hip_fpksk_generate(_ptr(out), _ptr(sk), _ptr(sk), p.k, p.N, level, base_log,
+                                             secure_std(p.k, p.N) if std is None else std, seed)
+    return out
+
+
+def fp_keyswitch(k: int, N: int, level: int, base_log: int, fpksk_dev, lwe_in, num_keys: int | None = None, out=None):
+    """fp-ks on device tensors: every row of lwe_in (rows, kN+1) through each of num_keys (default k + 1) keys of
+    fpksk_dev -> (rows, num_keys, (k+1)N) int64."""
+    torch = _torch()
+    device = lwe_in.device
+    rows = lwe_in.shape[0]
+    nk = k + 1 if num_keys is None else num_keys
+    if lwe_in.shape[1] != k * N + 1 or not lwe_in.is_contiguous():
+        raise ValueError(f"lwe_in: need a contiguous (rows, {k * N + 1}) tensor, got {tuple(lwe_in.shape)}")
+    if out is None:
+        out = torch.empty((rows, nk, (k + 1) * N), dtype=torch.int64, device=device)
+    _native.check(_native.lib().concrete_hip_fp_keyswitch(
+        _stream(device), _gpu_index(device), _ptr(out), _ptr(lwe_in), _ptr(fpksk_dev), k * N, k, N, base_log, level,
+        rows, nk), "concrete_hip_fp_keyswitch")
+    return out
+
+
+def circuit_bootstrap_supported(p: PbsParams, pksk_level: int, pksk_base_log: int, cbs_level: int,
+                                cbs_base_log: int) -> bool:
+    return bool(_native.lib().concrete_hip_circuit_bootstrap_supported(p.k, p.N, p.level, p.base_log, pksk_level,
+                                                                      pksk_base_log, cbs_level, cbs_base_log))
+
+
+def circuit_bootstrap_scratch_bytes(p: PbsParams, cbs_level: int, num_samples: int) -> int:
+    return int(_native.lib().concrete_hip_circuit_bootstrap_scratch_bytes(p.n, p.k, p.N, cbs_level, num_samples))
+
+
+def circuit_bootstrap(p: PbsParams, fbsk, fpksk_dev, lwe_in, delta_log: int, pksk_level: int, pksk_base_log: int,
+                      cbs_level: int, cbs_base_log: int, out=None, scratch=None, pbs_out=None):
+    """Circuit bootstrap on device tensors: lwe_in (samples, n+1), the bit at delta_log -> GGSWs
+    (samples, cbs_level, k+1, (k+1)N) int64, level matrix 0 being decomposition level 1 (what vertical_packing
+    reads).  pbs_out: optional (samples, cbs_level, kN+1) tensor that receives the rows the fp-ks reads."""
+    torch = _torch()
+    device = lwe_in.device
+    samples = lwe_in.shape[0]
+    if lwe_in.shape[1] != p.n + 1 or not lwe_in.is_contiguous():
+        raise ValueError(f"lwe_in: need a contiguous (samples, {p.n + 1}) tensor, got {tuple(lwe_in.shape)}")
+    if out is None:
+        out = torch.empty((samples, cbs_level, p.k + 1, p.glwe_size), dtype=torch.int64, device=device)
+    _native.check(_native.lib().concrete_hip_circuit_bootstrap(
+        _stream(device), _gpu_index(device), _ptr(out), _ptr(lwe_in), _ptr(fbsk), _ptr(fpksk_dev), delta_log, p.n, p.k,
+        p.N, p.level, p.base_log, pksk_level, pksk_base_log, cbs_level, cbs_base_log, samples, _ptr(scratch),
+        0 if scratch is None else scratch.numel() * scratch.element_size(), _ptr(pbs_out)),
+        "concrete_hip_circuit_bootstrap")
+    return out

@@ -155,6 +155,42 @@ void cuda_blind_rotate_and_sample_extraction_64(void *stream, uint32_t gpu_index
                                                 uint32_t base_log, uint32_t level_count, uint32_t max_shared_memory);
 void cleanup_cuda_blind_rotation_sample_extraction(void *stream, uint32_t gpu_index, int8_t **br_se_buffer);
 
+/* Circuit bootstrap, stage 2 of the WoP-PBS, and the private functional packing keyswitch (fp-ks) it ends
+ * with (concrete-cuda rust_api/src/cuda_bind.rs:334-364, 566-648).
+ * fp_ksk_array: [k+1 keys][kN+1 blocks][level][(k+1)N] words; block j < kN belongs to bit j of the flattened
+ * GLWE key, block kN to the constant -1; inside a block storage index t holds decomposition level `level - t`,
+ * as in this header's LWE keyswitch keys (concrete_hip_fpksk_generate writes one).
+ * cuda_fp_keyswitch_lwe_to_glwe_64: input row i (kN + 1 words) goes through key i mod number_of_keys and is
+ * written to GLWE i of glwe_array_out ([number_of_input_lwe][(k+1)N]).  The reference's implementation is not
+ * part of the sources this backend was written against; this is the reading under which the (k+1)-fold input
+ * buffer its circuit bootstrap documents composes with it.
+ * cuda_circuit_bootstrap_64: every input row (lwe_dimension + 1 words, the bit at delta_log) becomes one
+ * standard-domain GGSW of level_cbs x (k+1) x (k+1)N words; ggsw_out is [number_of_samples][level_cbs][k+1]
+ * [(k+1)N], level matrix 0 being decomposition level 1 (the order of one entry of a standard bootstrapping key
+ * and of cuda_cmux_tree_64's ggsw_in; newer tfhe versions store GGSW levels reversed).  fourier_bsk is as in
+ * cuda_extract_bits_64.  lut_vector_indexes: number_of_samples x level_cbs u64 entries on the device, as in
+ * cuda_programmable_bootstrap_lwe_ciphertext_vector_64, entry (sample, v) naming the level (0 .. level_cbs-1)
+ * whose test vector row (sample, v) uses; NULL stands for (sample, v) -> v.  `level_count` of the scratch call
+ * is level_cbs.  max_shared_memory is accepted and ignored.  A scratch call with allocate_gpu_memory = false
+ * leaves NULL, and a NULL buffer makes the call take stream-ordered pool scratch.  Bad arguments, unsupported
+ * parameters and a key that fails the PBS exactness gate abort. */
+void cuda_fp_keyswitch_lwe_to_glwe_64(void *stream, uint32_t gpu_index, void *glwe_array_out, const void *lwe_array_in,
+                                      const void *fp_ksk_array, uint32_t input_lwe_dimension,
+                                      uint32_t output_glwe_dimension, uint32_t output_polynomial_size,
+                                      uint32_t base_log, uint32_t level_count, uint32_t number_of_input_lwe,
+                                      uint32_t number_of_keys);
+void scratch_cuda_circuit_bootstrap_64(void *stream, uint32_t gpu_index, int8_t **cbs_buffer, uint32_t glwe_dimension,
+                                       uint32_t lwe_dimension, uint32_t polynomial_size, uint32_t level_count,
+                                       uint32_t number_of_inputs, uint32_t max_shared_memory,
+                                       bool allocate_gpu_memory);
+void cuda_circuit_bootstrap_64(void *stream, uint32_t gpu_index, void *ggsw_out, const void *lwe_array_in,
+                               const void *fourier_bsk, const void *fp_ksk_array, const void *lut_vector_indexes,
+                               int8_t *cbs_buffer, uint32_t delta_log, uint32_t polynomial_size,
+                               uint32_t glwe_dimension, uint32_t lwe_dimension, uint32_t level_bsk,
+                               uint32_t base_log_bsk, uint32_t level_pksk, uint32_t base_log_pksk, uint32_t level_cbs,
+                               uint32_t base_log_cbs, uint32_t number_of_samples, uint32_t max_shared_memory);
+void cleanup_cuda_circuit_bootstrap(void *stream, uint32_t gpu_index, int8_t **cbs_buffer);
+
 /* ------------------------------------------------------------------------------------------
  * Part 2: extensions (return 0 on success, < 0 on error; message via concrete_hip_last_error)
  * ------------------------------------------------------------------------------------------ */
@@ -169,7 +205,9 @@ void cleanup_cuda_blind_rotation_sample_extraction(void *stream, uint32_t gpu_in
  * Bit extraction (cuda_extract_bits_64, concrete_hip_extract_bits*) was added without a new version:
  * the value stays 5, and a caller finds the capability through concrete_hip_extract_bits_supported.
  * The same holds for vertical packing (cuda_cmux_tree_64, cuda_blind_rotate_and_sample_extraction_64,
- * concrete_hip_vertical_packing*): concrete_hip_vertical_packing_supported. */
+ * concrete_hip_vertical_packing*): concrete_hip_vertical_packing_supported; and for the circuit bootstrap
+ * (cuda_circuit_bootstrap_64, cuda_fp_keyswitch_lwe_to_glwe_64, concrete_hip_circuit_bootstrap*,
+ * concrete_hip_fp_keyswitch): concrete_hip_circuit_bootstrap_supported. */
 uint32_t concrete_hip_abi_version(void);
 /* thread-local message of the last failed concrete_hip_* call */
 const char *concrete_hip_last_error(void);
@@ -319,6 +357,51 @@ uint64_t concrete_hip_vertical_packing_scratch_bytes(uint32_t glwe_dimension, ui
 /* 1 for N = 512, 1024, 2048, k <= 3 and a (level, base_log) the general path keeps exact, else 0 */
 int concrete_hip_vertical_packing_supported(uint32_t glwe_dimension, uint32_t polynomial_size, uint32_t level_count,
                                             uint32_t base_log);
+/* Private functional packing keyswitch with a status code: every one of num_rows LWE rows
+ * (lwe_dimension_in + 1 = kN + 1 words, body last) goes through every one of the num_keys keys of fp_ksk (the
+ * layout above with num_keys keys; the circuit bootstrap uses k + 1):
+ *   glwe_array_out[r][i] = - sum_{j = 0 .. kN} sum_level d(x_r[j], level) * fp_ksk[i][j][level]   (mod 2^64)
+ * with d the balanced signed decomposition of every word, the body included, and no body term added: the
+ * library's LWE keyswitch of the row (x_r, 0) with n_in = kN + 1 and n_out + 1 = (k+1)N, word for word.
+ * glwe_array_out is [num_rows][num_keys][(k+1)N].  Any (level, base_log) with level * base_log < 64.
+ * Stream-ordered.  Checked before the first device call: -1 null pointer; -3 num_keys == 0,
+ * lwe_dimension_in != k N, sizes that overflow; -2 parameters for which concrete_hip_keyswitch_supported(level,
+ * base_log, kN + 1, (k+1)N - 1) is 0.  Nothing is written by a refused call. */
+int concrete_hip_fp_keyswitch(void *stream, uint32_t gpu_index, uint64_t *glwe_array_out, const uint64_t *lwe_array_in,
+                              const uint64_t *fp_ksk, uint32_t lwe_dimension_in, uint32_t glwe_dimension,
+                              uint32_t polynomial_size, uint32_t base_log, uint32_t level_count, uint32_t num_rows,
+                              uint32_t num_keys);
+/* Circuit bootstrap with a status code.  Per input row c (lwe_dimension + 1 words) and
+ * v = 0 .. level_cbs-1, level = v + 1: u = c * 2^(63 - delta_log) with 2^62 added to the body;
+ * w = PBS(u, acc_v), acc_v the trivial GLWE whose body coefficients all are -(2^(63 - base_log_cbs * level));
+ * w.body += 2^(63 - base_log_cbs * level); row i (0 .. k) of level matrix v of the output GGSW is the fp-ks
+ * of w with key i.  ggsw_out is [num_samples][level_cbs][k+1][(k+1)N], level matrix 0 being decomposition
+ * level 1 (the order concrete_hip_vertical_packing reads).  pbs_out: optional [num_samples][level_cbs][kN+1],
+ * the rows w after the body constant (what the fp-ks reads).  Every pointer is device memory; fourier_bsk as
+ * in concrete_hip_pbs.  scratch: 16-byte aligned, at least concrete_hip_circuit_bootstrap_scratch_bytes()
+ * bytes, or NULL for stream-ordered pool scratch.  One batched PBS over num_samples * level_cbs rows, then one
+ * fp-ks; stream-ordered, no host synchronisation, device-to-host copy or allocation in between.
+ * Checked before the first device call: -1 null pointer; -3 delta_log > 63, sizes that overflow, a scratch
+ * buffer too small or misaligned; -2 parameters for which concrete_hip_circuit_bootstrap_supported is 0 (also:
+ * a key that fails the PBS exactness gate).  Nothing is written by a refused call. */
+int concrete_hip_circuit_bootstrap(void *stream, uint32_t gpu_index, uint64_t *ggsw_out, const uint64_t *lwe_array_in,
+                                   const void *fourier_bsk, const uint64_t *fp_ksk, uint32_t delta_log,
+                                   uint32_t lwe_dimension, uint32_t glwe_dimension, uint32_t polynomial_size,
+                                   uint32_t level_bsk, uint32_t base_log_bsk, uint32_t level_pksk,
+                                   uint32_t base_log_pksk, uint32_t level_cbs, uint32_t base_log_cbs,
+                                   uint32_t num_samples, void *scratch, uint64_t scratch_bytes, uint64_t *pbs_out);
+/* scratch bytes of such a call; 0 for num_samples == 0, level_cbs == 0, lwe_dimension == 0, (k+1)N == 0 or
+ * above 65536, or sizes that overflow.  Does not decrease with num_samples or level_cbs. */
+uint64_t concrete_hip_circuit_bootstrap_scratch_bytes(uint32_t lwe_dimension, uint32_t glwe_dimension,
+                                                      uint32_t polynomial_size, uint32_t level_cbs,
+                                                      uint32_t num_samples);
+/* 1 exactly when concrete_hip_pbs_supported(k, N, level_bsk, base_log_bsk), concrete_hip_keyswitch_supported(
+ * level_pksk, base_log_pksk, kN + 1, (k+1)N - 1), level_cbs >= 1 and level_cbs * base_log_cbs <= 63 all hold */
+int concrete_hip_circuit_bootstrap_supported(uint32_t glwe_dimension, uint32_t polynomial_size, uint32_t level_bsk,
+                                             uint32_t base_log_bsk, uint32_t level_pksk, uint32_t base_log_pksk,
+                                             uint32_t level_cbs, uint32_t base_log_cbs);
+/* u64 words of the list of k + 1 fp-ks keys: (k+1) (kN+1) level (k+1)N; 0 when that overflows 64 bits */
+uint64_t concrete_hip_fpksk_size_words(uint32_t glwe_dimension, uint32_t polynomial_size, uint32_t level_count);
 /* Fourier key registered for a `dest` of cuda_convert_lwe_programmable_bootstrap_key_64, or NULL */
 const void *concrete_hip_lookup_bsk(const void *bootstrapping_key);
 /* Release what the backend derived from device buffer `ptr` (a registered Fourier key whose `dest`
@@ -387,6 +470,14 @@ void concrete_hip_bsk_generate(uint64_t *bsk, const uint64_t *lwe_sk, const uint
                                uint64_t k, uint64_t N, uint64_t l, uint64_t logB, double std_torus, uint64_t seed);
 void concrete_hip_ksk_generate(uint64_t *ksk, const uint64_t *sk_in, const uint64_t *sk_out, uint64_t n_in,
                                uint64_t n_out, uint64_t l, uint64_t logB, double std_torus, uint64_t seed);
+/* The list of k + 1 fp-ks keys of the circuit bootstrap (concrete_hip_fpksk_size_words(k, N, l) words, the
+ * layout given with cuda_fp_keyswitch_lwe_to_glwe_64).  lwe_sk_in: the kN bits of the input LWE key, which is the
+ * flattened GLWE key the PBS output is under; glwe_sk: the output GLWE key.  Entry (i, j, t) is a GLWE
+ * encryption of -s_j 2^(64 - logB (l - t)) P_i, P_i = polynomial i of glwe_sk for i < k, P_k = the constant -1,
+ * s_kN = -1.  Parallel over the (i, j) blocks, block b = i (kN + 1) + j seeded with
+ * seed ^ (0x2545f491 * (b + 1)). */
+void concrete_hip_fpksk_generate(uint64_t *fpksk, const uint64_t *lwe_sk_in, const uint64_t *glwe_sk, uint64_t k,
+                                 uint64_t N, uint64_t l, uint64_t logB, double std_torus, uint64_t seed);
 void concrete_hip_encode_expand_lut(uint64_t *out, uint64_t out_size, const uint64_t *in, uint64_t in_size,
                                     uint32_t out_message_bits, int is_signed);
 
