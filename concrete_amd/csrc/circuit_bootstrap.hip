@@ -35,9 +35,10 @@
 namespace chip {
 
 // ------------------------------------------------------------------------------------------
-// fp-ks.  Wide digits (base_log 10 .. 25 in the optimizer's tables, never the int8 matrix-core range), a
-// key of hundreds of MB and few rows: a workgroup keeps FPKS_ROWS rows x FPKS_THREADS columns of u64 sums
-// in registers and streams its slice of the key once for all of them.
+// fp-ks.  Mostly wide digits (base_log 6 .. 24 at 8 .. 1 levels in the optimizer's WoP table; 8 of its 272
+// rows, at (6, 7) and (8, 6), have digits as narrow as the int8 matrix-core keyswitch takes), a key of
+// hundreds of MB and few rows: a workgroup keeps FPKS_ROWS rows x FPKS_THREADS columns of u64 sums in
+// registers and streams its slice of the key once for all of them.
 //
 // Digits are stored offset, e = d + B/2 in [0, B] (B = 2^base_log): unsigned, so the low 64 bits of e * key
 // are one 32 x 32 -> 64 multiply-add and one (DIG = uint32_t, base_log <= 31) or two (uint64_t) 32-bit

@@ -3,12 +3,16 @@ declares, its host-side client helpers agree bit-for-bit with the oracle, and it
 status-returning entry points reject bad arguments before touching a device."""
 import ctypes as C
 import os
+import sys
 
 import numpy as np
 import pytest
 
 from concrete_amd import _native
 from concrete_amd import backend as B
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import table_shapes as S  # noqa: E402
 
 
 def test_library_exports_every_declared_symbol():
@@ -222,3 +226,78 @@ def test_optimizer_rows_on_hand_tuned_kernels():
             assert r["N"] == 2048 and r["br_l"] >= 5, r
         if fmt(r) != 3:
             assert L.concrete_hip_pbs_supported(r["k"], r["N"], r["br_l"], r["br_b"]) == 1, r
+
+
+def test_table_shape_lists_are_complete():
+    """tests/table_shapes.py: the counts of distinct shapes in the optimizer's two tables and in their unions,
+    every list sorted and free of repeats, and the general path's 37 dispatch classes."""
+    assert len(S.V0_ROWS) == 235 and len(S.V0_PBS) == 91 and len(S.V0_KS) == 26
+    assert len(S.WOP_ROWS) == 272 and len(S.WOP_BSK) == 17 and len(S.WOP_KS) == 11
+    assert len(S.WOP_CB) == 20 and len(S.WOP_PP) == 7
+    assert len(S.PBS_SHAPES) == 99 and len(S.KS_DECOMPS) == 29
+    assert {(r["k"], r["N"]) for r in S.WOP_ROWS} == {S.WOP_RING}
+    assert all(set(r) == {"bits", "log_norm2", "k", "N", "n", "br_l", "br_b", "ks_l", "ks_b", "cb_l", "cb_b", "pp_l",
+                          "pp_b"} and all(type(v) is int for v in r.values()) for r in S.WOP_ROWS)
+    for lst in (S.V0_PBS, S.V0_KS, S.WOP_BSK, S.WOP_KS, S.WOP_CB, S.WOP_PP, S.PBS_SHAPES, S.KS_DECOMPS):
+        assert lst == sorted(set(lst))
+    assert S.WOP_CB[0] == (1, 10) and (1, 14) in S.WOP_CB and S.WOP_CB[-1] == (32, 1)
+    assert S.WOP_PP == [(1, 24), (2, 16), (3, 12), (4, 10), (5, 8), (6, 7), (8, 6)]
+    # the eight BSK decompositions the WoP table adds to the v0 table's on its ring
+    assert [s[2:] for s in S.PBS_SHAPES if s not in S.V0_PBS] == [(9, 5), (10, 4), (14, 3), (21, 2), (22, 2), (23, 2),
+                                                                  (43, 1), (45, 1)]
+    # the general path's dispatch classes (pbs_generic.hip) over the v0 table: (N, (k+1) l up to 8 or above,
+    # limbs, sub-digits T = ceil(base_log / limb bits), 32-bit decomposer state when l base_log <= 31)
+    L = _native.lib()
+
+    def generic_class(shape):
+        k, N, level, base_log = shape
+        limbs, bits = C.c_uint32(), C.c_uint32()
+        if L.concrete_hip_bsk_format(k, N, level, C.byref(limbs), C.byref(bits)) != 3:
+            return None
+        return N, min((k + 1) * level, 9), limbs.value, -(-base_log // bits.value), level * base_log <= 31
+
+    general = [s for s in S.V0_PBS if generic_class(s)]
+    assert len(general) == 55 and len({generic_class(s) for s in general}) == 37
+    assert generic_class((1, 8192, 10, 4)) == (8192, 9, 4, 1, False)
+    assert generic_class((1, 4096, 1, 22)) == (4096, 2, 5, 2, True)
+    assert all(generic_class(s) is None for s in S.WOP_BSK)  # the WoP table's ring has a kernel of its own
+
+
+def test_wop_table_coverage():
+    """Every row of the optimizer's WoP-PBS table (tests/golden/wop_pbs_last_128_rows.json, from
+    v0-parameters/ref/wop_pbs_last_128 by tests/golden/make_wop_rows.py) is accepted, with the row's own
+    numbers, by the predicates of the PBS, the keyswitch and the three WoP-PBS stages."""
+    L = _native.lib()
+    checks = {
+        "pbs": lambda r: L.concrete_hip_pbs_supported(r["k"], r["N"], r["br_l"], r["br_b"]),
+        "keyswitch": lambda r: L.concrete_hip_keyswitch_supported(r["ks_l"], r["ks_b"], r["k"] * r["N"], r["n"]),
+        "extract_bits": lambda r: L.concrete_hip_extract_bits_supported(
+            r["k"] * r["N"], r["n"], r["k"], r["N"], r["br_b"], r["br_l"], r["ks_b"], r["ks_l"]),
+        "circuit_bootstrap": lambda r: L.concrete_hip_circuit_bootstrap_supported(
+            r["k"], r["N"], r["br_l"], r["br_b"], r["pp_l"], r["pp_b"], r["cb_l"], r["cb_b"]),
+        "vertical_packing": lambda r: L.concrete_hip_vertical_packing_supported(r["k"], r["N"], r["cb_l"], r["cb_b"]),
+    }
+    assert len(S.WOP_ROWS) == 272
+    for name, accepts in checks.items():
+        assert [r for r in S.WOP_ROWS if accepts(r) != 1] == [], name
+
+
+def test_wop_ggsw_key_formats():
+    """The general key formats the CMUX kernel runs the WoP table's 20 GGSW decompositions on at k = 2,
+    N = 1024 (concrete_hip_bsk_format answers the ring's own kernel there, so the limb chooser is read through
+    its restatement oracle/keyref.generic_limb_bits, as tests/vp_reference.py does): seven (limbs, bits), and
+    two sub-digits at (1, 14) only."""
+    from oracle import keyref
+
+    k, N = S.WOP_RING
+    fmt, two = {}, []
+    for level, base_log in S.WOP_CB:
+        assert _native.lib().concrete_hip_bsk_format(k, N, level, C.byref(C.c_uint32()), C.byref(C.c_uint32())) == 4
+        bits = keyref.generic_limb_bits(k, N, level)
+        fmt[(level, base_log)] = (-(-64 // bits), bits)
+        if -(-base_log // bits) > 1:
+            two.append((level, base_log))
+    assert sorted(set(fmt.values())) == [(4, 16), (4, 19), (4, 20), (4, 21), (5, 13), (5, 14), (6, 12)]
+    assert two == [(1, 14)]
+    assert fmt[(1, 14)] == (5, 13) and fmt[(4, 6)] == (6, 12) and fmt[(5, 5)] == (5, 14) and fmt[(6, 5)] == (4, 16)
+    assert fmt[(10, 3)] == (4, 19) and fmt[(16, 2)] == (4, 20) and fmt[(32, 1)] == (4, 21)
