@@ -211,10 +211,11 @@ constexpr int KSL_ROWS = 128, KSL_COLS = 64, KSL_KB = 64, KSL_RS = 3;
 __global__ void __launch_bounds__(256) ks_digits_i8_kernel(int8_t* __restrict__ A, const uint64_t* __restrict__ in,
                                                          const uint64_t* __restrict__ in_idx, uint32_t n_in,
                                                          uint32_t level, uint32_t base_log, uint32_t num_samples,
-                                                         uint32_t Ks, uint32_t ipr) {
+                                                         uint32_t Ks, uint32_t ipr, uint32_t rows) {
   // thread = (sample row b, mask position i); rows past the batch and positions past n_in: zeros
   const uint64_t g = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
   const uint32_t b = (uint32_t)(g / ipr), i = (uint32_t)(g % ipr);
+  if (b >= rows) return;  // the last workgroup's threads past rows * ipr (an odd ipr): A has `rows` rows
   const int nrep = 64 - (int)(level * base_log);
   uint64_t a = 0ull;
   if (b < num_samples && i < n_in) a = Rows<const uint64_t>{in, in_idx, n_in + 1}.at(b, i);
@@ -535,7 +536,7 @@ static int keyswitch_mfma_launch(const KsArgs& a) {
     const uint32_t Bp = (p.num_samples + KSL_ROWS - 1) / KSL_ROWS * KSL_ROWS;
     const uint64_t nd = (uint64_t)Bp * ipr;
     hipLaunchKernelGGL(ks_digits_i8_kernel, dim3((uint32_t)((nd + 255) / 256)), dim3(256), 0, p.stream, A, p.in,
-                       p.in_idx, p.n_in, p.level, p.base_log, p.num_samples, Ks, ipr);
+                       p.in_idx, p.n_in, p.level, p.base_log, p.num_samples, Ks, ipr, Bp);
     if (splits > 1) launch_zero(p);
     hipLaunchKernelGGL(ks_mfma_lds_kernel, dim3(NP / KSL_COLS, Bp / KSL_ROWS, splits), dim3(512), KSL_LDS, p.stream,
                        p.out, p.out_idx, p.in, p.in_idx, A, Bt, p.n_in, p.n_out, p.num_samples, NP, Kp, Ks, k_per_split);

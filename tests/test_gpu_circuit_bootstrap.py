@@ -17,6 +17,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import cbs_reference as R  # noqa: E402
+import table_shapes as S  # noqa: E402
 import vp_reference as V  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -71,21 +72,24 @@ def _filled(env, shape):
 # ---------------------------------------------------------------------------------------------------------
 FPKS_SHAPES = [(1, 256), (2, 512)]
 FPKS_DECOMP = [(1, 25), (2, 15), (3, 13), (4, 10), (2, 31), (1, 40)]  # the last: a digit beyond 32 bits
+# and the WoP table's seven (pp_l, pp_b), up to 8 levels: (4, 10) is in the list above already
+FPKS_DECOMP += [d for d in S.WOP_PP if d not in FPKS_DECOMP]
 ROW_COUNTS = (1, 2, T - 1, T, T + 1, 2 * T + 1)
 MAX_ROWS = 2 * T + 1
 
 
-def _fpks_case(env, k, N, level, base_log):
+def _fpks_case(env, k, N, level, base_log, keys=None, max_rows=MAX_ROWS):
     """Random key words (the map is linear: any words pin it), random rows with the decomposition's edge values
-    in row 0 and 1, the reference for MAX_ROWS rows and k + 1 keys, and the key on the device."""
-    key = (k, N, level, base_log)
+    in row 0 and 1, the reference for max_rows rows and `keys` (k + 1 unless given) keys, and the key on the device."""
+    keys = k + 1 if keys is None else keys
+    key = (k, N, level, base_log, keys, max_rows)
     if key in env["fpks"]:
         return env["fpks"][key]
     B = env["B"]
     rng = np.random.RandomState(9400 + 1000 * k + N + 17 * level + base_log)
     W, G = k * N + 1, (k + 1) * N
-    fpksk = _rand_u64(rng, (k + 1, W, level, G))
-    rows = _rand_u64(rng, (MAX_ROWS, W))
+    fpksk = _rand_u64(rng, (keys, W, level, G))
+    rows = _rand_u64(rng, (max_rows, W))
     nrep = 64 - level * base_log
     q = _rand_u64(rng, 8) >> np.uint64(nrep)
     half_step = (q << np.uint64(nrep)) | np.uint64(1 << (nrep - 1))  # the dropped bits are exactly half a step
@@ -119,6 +123,24 @@ def test_fp_keyswitch_bit_exact(env, shape, decomp):
             got = B.to_host(out)
             assert np.array_equal(got[:rows], c["want"][:rows, :nk]), f"{rows} rows, {nk} keys"
             assert (got[rows] == np.uint64(SENTINEL)).all(), f"{rows} rows, {nk} keys: wrote past the output"
+
+
+@pytest.mark.parametrize("decomp", S.WOP_PP, ids=lambda d: f"l{d[0]}b{d[1]}")
+def test_fp_keyswitch_at_the_table_ring(env, decomp):
+    """The WoP table's own ring (k = 2, N = 1024: 2049 blocks, 3072 output words) at each of its (pp_l, pp_b), one
+    key of random words (403 MB at 8 levels), one row and one row more than a workgroup's tile."""
+    B, torch = env["B"], env["torch"]
+    (k, N), (level, base_log) = S.WOP_RING, decomp
+    counts = (1, T + 1)
+    c = _fpks_case(env, k, N, level, base_log, keys=1, max_rows=max(counts))
+    G = (k + 1) * N
+    for rows in counts:
+        out = _filled(env, (rows + 1, 1, G))  # one GLWE row more than the call writes
+        B.fp_keyswitch(k, N, level, base_log, c["d_key"], B.to_device(c["rows"][:rows].copy(), DEV), num_keys=1, out=out)
+        torch.cuda.synchronize()
+        got = B.to_host(out)
+        assert np.array_equal(got[:rows], c["want"][:rows]), f"{rows} rows"
+        assert (got[rows] == np.uint64(SENTINEL)).all(), f"{rows} rows: wrote past the output"
 
 
 def test_fp_keyswitch_unsplit_row_count(env):
@@ -173,12 +195,14 @@ MAX_LEVEL_CBS, MAX_SAMPLES = 4, 5
 CBS_RUNS = [(1, 1, 63), (2, 3, 59), (4, 5, 63), (4, 1, 59), (2, 5, 63), (1, 3, 59)]
 
 
-def _cbs_keys(env, shape):
-    """Secret keys, the standard and the device BSK and the fp-ks key list of a shape, once per module."""
-    if shape in env["keys"]:
-        return env["keys"][shape]
+def _cbs_keys(env, shape, pp=None):
+    """Secret keys, the standard and the device BSK and the fp-ks key list of a shape, at the shape's own fp-ks
+    decomposition or at pp = (level, base_log); kept until another (shape, pp) is asked for."""
+    if (shape, pp) in env["keys"]:
+        return env["keys"][(shape, pp)]
     B, O = env["B"], env["O"]
     (k, N, n), (bl, bb), (pl, pb), _, real = CBS_SHAPES[shape]
+    pl, pb = pp or (pl, pb)
     seed = 9500 + 10 * sorted(CBS_SHAPES).index(shape)
     p = B.PbsParams(n=n, k=k, N=N, level=bl, base_log=bb)
     lwe_sk, glwe_sk = B.binary_key(n, seed), B.binary_key(k * N, seed + 1)
@@ -189,7 +213,7 @@ def _cbs_keys(env, shape):
         fpksk = _rand_u64(np.random.RandomState(seed + 3), (k + 1, k * N + 1, pl, (k + 1) * N))
     e = dict(p=p, lwe_sk=lwe_sk, glwe_sk=glwe_sk, bsk=bsk, fpksk=fpksk, fbsk=B.convert_bsk(p, bsk, DEV),
              d_fpksk=B.to_device(fpksk.reshape(-1), DEV))
-    env["keys"] = {shape: e}  # one shape's keys on the device at a time
+    env["keys"] = {(shape, pp): e}  # one shape's keys on the device at a time
     return e
 
 
@@ -215,29 +239,56 @@ def _cbs_case(env, shape, delta_log):
 @pytest.mark.parametrize("run", CBS_RUNS, ids=lambda r: f"l{r[0]}s{r[1]}d{r[2]}")
 @pytest.mark.parametrize("shape", sorted(CBS_SHAPES))
 def test_circuit_bootstrap_bit_exact(env, shape, run):
-    B, torch = env["B"], env["torch"]
     level_cbs, samples, delta_log = run
-    (k, N, n), _, (pl, pb), cb, _ = CBS_SHAPES[shape]
+    _, _, (pl, pb), cb, _ = CBS_SHAPES[shape]
     e = _cbs_keys(env, shape)
     c = _cbs_case(env, shape, delta_log)
-    p = e["p"]
+    _run_and_compare(env, e, c["cts"][:samples], delta_log, (pl, pb), (level_cbs, cb), c["ggsw"][:samples, :level_cbs],
+                     c["w"][:samples, :level_cbs], own_scratch=samples == 3)
+
+
+def _run_and_compare(env, e, cts, delta_log, pp, cbs, want_ggsw, want_w, own_scratch=False):
+    """One circuit bootstrap of the rows `cts` with the keys `e`: the rows after the PBS and the GGSWs equal the
+    reference, the GLWE and the row past the call's output keep the sentinel, the stream's status is clean."""
+    B, torch = env["B"], env["torch"]
+    p, samples, (pl, pb), (level_cbs, cb) = e["p"], cts.shape[0], pp, cbs
+    k, N = p.k, p.N
     assert B.circuit_bootstrap_supported(p, pl, pb, level_cbs, cb)
     out = _filled(env, (samples + 1, level_cbs, k + 1, (k + 1) * N))
     w = _filled(env, (samples + 1, level_cbs, k * N + 1))
     scratch = None
-    if samples == 3:  # the caller's scratch, exactly the size the query names; elsewhere the pool's
+    if own_scratch:  # the caller's scratch, exactly the size the query names; elsewhere the pool's
         need = B.circuit_bootstrap_scratch_bytes(p, level_cbs, samples)
         assert need > 0 and need % 16 == 0
         scratch = torch.empty(need // 8, dtype=torch.int64, device=DEV)
-    B.circuit_bootstrap(p, e["fbsk"], e["d_fpksk"], B.to_device(c["cts"][:samples].copy(), DEV), delta_log, pl, pb,
-                        level_cbs, cb, out=out, scratch=scratch, pbs_out=w)
+    B.circuit_bootstrap(p, e["fbsk"], e["d_fpksk"], B.to_device(cts.copy(), DEV), delta_log, pl, pb, level_cbs, cb,
+                        out=out, scratch=scratch, pbs_out=w)
     torch.cuda.synchronize()
     assert B.stream_status(DEV) == 0
     got_w, got = B.to_host(w), B.to_host(out)
-    assert np.array_equal(got_w[:samples], c["w"][:samples, :level_cbs]), "the rows after the PBS differ (before the fp-ks)"
-    assert np.array_equal(got[:samples], c["ggsw"][:samples, :level_cbs]), "the GGSWs differ (in the fp-ks)"
+    assert np.array_equal(got_w[:samples], want_w), "the rows after the PBS differ (before the fp-ks)"
+    assert np.array_equal(got[:samples], want_ggsw), "the GGSWs differ (in the fp-ks)"
     sentinel = np.uint64(SENTINEL)
     assert (got_w[samples] == sentinel).all() and (got[samples] == sentinel).all(), "wrote past the output"
+
+
+# The WoP table's 32 distinct (cb_l, cb_b, pp_l, pp_b), ordered by (pp, cb) so that one fp-ks key serves its run of
+# pairs: all of them on n512 with a real fp-ks key, those of at most 2 fp-ks levels (a key list of <= 302 MB) on
+# the table's own ring with random key words.  Each runs at level_cbs = cb_l (up to 32; CBS_RUNS stop at 4).
+CBS_TABLE_PAIRS = sorted(S.distinct(S.WOP_ROWS, "cb_l", "cb_b", "pp_l", "pp_b"), key=lambda q: (q[2:], q[:2]))
+CBS_TABLE_CASES = [("n512", q) for q in CBS_TABLE_PAIRS] + [("k2n1024", q) for q in CBS_TABLE_PAIRS if q[2] <= 2]
+
+
+@pytest.mark.parametrize("case", CBS_TABLE_CASES, ids=lambda c: "%s-cb%d_%d-pp%d_%d" % ((c[0],) + c[1]))
+def test_circuit_bootstrap_table_pairs(env, case):
+    B = env["B"]
+    shape, (cb_l, cb_b, pl, pb) = case
+    (k, N, n), (bl, bb), _, _, _ = CBS_SHAPES[shape]
+    e = _cbs_keys(env, shape, pp=(pl, pb))
+    delta_log = (63, 59)[CBS_TABLE_PAIRS.index(case[1]) % 2]
+    cts = B.lwe_encrypt(e["lwe_sk"], [b << delta_log for b in (1, 0)], n, KEY_STD, 9650 + delta_log)
+    ggsw, w = R.circuit_bootstrap(cts, e["bsk"], e["fpksk"], delta_log, n, k, N, bl, bb, pl, pb, cb_l, cb_b)
+    _run_and_compare(env, e, cts, delta_log, (pl, pb), (cb_l, cb_b), ggsw, w)
 
 
 @pytest.mark.parametrize("with_buffer", (True, False), ids=("buffer", "null"))

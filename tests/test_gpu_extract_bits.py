@@ -41,7 +41,21 @@ def env():
     return dict(torch=torch, L=_native.lib(), B=B, O=O, N=_native, setups={})
 
 
+# Three rows of the optimizer's WoP table (tests/golden/wop_pbs_last_128_rows.json; k = 2, N = 1024), each with
+# its own BSK and keyswitch decomposition, n cut to 8: name -> (bits, log_norm2, br_l, br_b, ks_l, ks_b).
+# tests/test_keygen_abi.py holds them to the table.
+WOP_ROWS = {
+    "wop_fewest_bsk_levels": (1, 0, 2, 15, 3, 3),       # the fewest BSK levels of the table
+    "wop_most_bsk_levels": (2, 20, 45, 1, 13, 1),       # the most
+    "wop_deepest_keyswitch": (10, 14, 22, 2, 15, 1),    # the most keyswitch levels of the table
+}
+NAMES = ["cfg2", "cfg4", "opt1", "cfg2_full"] + list(WOP_ROWS)
+
+
 def _shape(B, name):
+    if name in WOP_ROWS:
+        _, _, br_l, br_b, ks_l, ks_b = WOP_ROWS[name]
+        return B.PbsParams(n=8, k=2, N=1024, level=br_l, base_log=br_b, ks_level=ks_l, ks_base_log=ks_b)
     return {"cfg2": replace(B.CFG2, n=8), "cfg4": replace(B.CFG4, n=8), "opt1": replace(B.OPTIMIZER_SETS[1], n=8),
             "cfg2_full": B.CFG2}[name]
 
@@ -53,7 +67,7 @@ def _setup(env, name):
         return env["setups"][name]
     B, O, torch = env["B"], env["O"], env["torch"]
     p = _shape(B, name)
-    seed = 7100 + 10 * sorted(["cfg2", "cfg4", "opt1", "cfg2_full"]).index(name)
+    seed = 7100 + 10 * sorted(NAMES).index(name)
     lwe_sk = B.binary_key(p.n, seed)
     glwe_sk = B.binary_key(p.big_n, seed + 1)
     bsk = B.bsk_generate(p, lwe_sk, glwe_sk, seed + 2, std=KEY_STD)
@@ -169,9 +183,10 @@ def _decrypt_bits(env, S, out_words):
 
 
 # ------------------------------------------------------------------------------------------------
-# 1. bit-exact against the oracle composition: the N = 1024 and N = 2048 kernels, and a k > 1 shape
+# 1. bit-exact against the oracle composition: the N = 1024 and N = 2048 kernels, a k > 1 shape, and three
+#    rows of the WoP table at its own ring
 # ------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", ["cfg2", "cfg4", "opt1"])
+@pytest.mark.parametrize("name", ["cfg2", "cfg4", "opt1"] + list(WOP_ROWS))
 def test_bit_exact_against_oracle(env, name):
     B, torch = env["B"], env["torch"]
     S = _setup(env, name)

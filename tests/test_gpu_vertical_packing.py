@@ -6,7 +6,8 @@ sample extraction, every external product the oracle's integer one.  The device 
 so every comparison here is word for word; there is no tolerance anywhere.  GGSWs are near-noiseless
 (sigma 2^-52, as tests/test_gpu_extract_bits.py); the bit-exact checks do not depend on the noise, the decrypt
 check keeps every phase inside its window.  Outputs are sentinel-filled before each call.  References are
-computed once per (shape, geometry) and shared.
+computed once per (shape, geometry) and shared.  Besides the small shapes, the optimizer's WoP table runs at its
+own ring, k = 2, N = 1024, with each of its 20 GGSW decompositions (tests/table_shapes.py).
 
 One bound is not taken through the ABI: concrete_hip_generic_error_bound answers -1 for a (k, N, level) whose
 primary key format is a hand-tuned kernel's (tests/test_keygen_abi.py asserts that), which (1, 1024, 3) and
@@ -21,6 +22,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import table_shapes as S  # noqa: E402
 import vp_reference as V  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -33,6 +35,11 @@ SENTINEL = 0x5A5A5A5A5A5A5A5A
 # on the 13-bit limbs of (1, 1024, 2))
 SHAPES = {"n512": (1, 512, 2, 10), "n1024": (1, 1024, 3, 8), "n2048": (1, 2048, 2, 12), "k2n512": (2, 512, 2, 10),
           "n1024t2": (1, 1024, 2, 15)}
+# the WoP table's own ring (k = 2, N = 1024) at each of its 20 GGSW decompositions (cb_l, cb_b), up to 32 levels
+WOP_SHAPES = {"wop_l%db%d" % d: S.WOP_RING + d for d in S.WOP_CB}
+# one of them per general key format the CMUX kernel runs them on (tests/test_keygen_abi.py::
+# test_wop_ggsw_key_formats): (limbs, bits) = (5,13) with two sub-digits, (6,12), (5,14), (4,16), (4,19), (4,20), (4,21)
+WOP_FORMAT_SHAPES = ["wop_l%db%d" % d for d in [(1, 14), (4, 6), (5, 5), (6, 5), (10, 3), (16, 2), (32, 1)]]
 
 
 def _geoms(N):
@@ -45,7 +52,7 @@ CASES = [("n1024", g) for g in _geoms(1024)] + [
     ("n512", (3, 4, 3, 3)), ("n512", (0, 9, 2, 1)),
     ("n2048", (3, 4, 3, 3)), ("n2048", (2, 1, 1, 2)),
     ("k2n512", (3, 4, 3, 3)), ("k2n512", (0, 9, 2, 1)),
-    ("n1024t2", (3, 4, 3, 3)), ("n1024t2", (3, 0, 3, 1))]
+    ("n1024t2", (3, 4, 3, 3)), ("n1024t2", (3, 0, 3, 1))] + [(name, (3, 4, 3, 3)) for name in WOP_SHAPES]
 
 
 def _case_id(c):
@@ -64,15 +71,20 @@ def env():
 
 
 def _params(env, shape):
-    k, N, level, base_log = SHAPES[shape]
+    k, N, level, base_log = SHAPES[shape] if shape in SHAPES else WOP_SHAPES[shape]
     return env["B"].PbsParams(n=1, k=k, N=N, level=level, base_log=base_log)
+
+
+def _index(shape):
+    """A shape's number in the seeds: SHAPES sorted by name, then WOP_SHAPES in the table's order."""
+    return sorted(SHAPES).index(shape) if shape in SHAPES else len(SHAPES) + list(WOP_SHAPES).index(shape)
 
 
 def _key(env, shape):
     """The GLWE secret key of a shape, generated once per module."""
     if shape not in env["keys"]:
         p = _params(env, shape)
-        env["keys"][shape] = env["O"].binary_key(p.k * p.N, 8100 + sorted(SHAPES).index(shape))
+        env["keys"][shape] = env["O"].binary_key(p.k * p.N, 8100 + _index(shape))
     return env["keys"][shape]
 
 
@@ -95,7 +107,7 @@ def _case(env, shape, geom, messages=False):
         return env["cases"][key]
     p = _params(env, shape)
     r, m, tau, lookups = geom
-    rng = np.random.RandomState(8200 + 31 * sorted(SHAPES).index(shape) + 7 * r + 3 * m + tau + 101 * lookups)
+    rng = np.random.RandomState(8200 + 31 * _index(shape) + 7 * r + 3 * m + tau + 101 * lookups)
     bits = _patterns(rng, r + m, lookups)
     ggsws = V.ggsw_encrypt(_key(env, shape), bits, p.k, p.N, p.level, p.base_log, KEY_STD, 8300 + 13 * r + m)
     if messages:
@@ -110,7 +122,8 @@ def _case(env, shape, geom, messages=False):
         c["lwe"], c["tree"] = V.vertical_packing(ggsws, luts, r, m, p.k, p.N, p.level, p.base_log)
         for a in (c["lwe"], c["tree"], ggsws, luts):
             a.setflags(write=False)
-    env["cases"][key] = c
+    if shape in SHAPES or shape in WOP_FORMAT_SHAPES:  # the other WoP shapes have one test each
+        env["cases"][key] = c
     return c
 
 
@@ -148,7 +161,7 @@ def test_bit_exact_against_the_reference(env, case):
     assert np.array_equal(lwe, c["lwe"]), "the extracted LWEs differ from the reference"
 
 
-@pytest.mark.parametrize("shape", sorted(SHAPES))
+@pytest.mark.parametrize("shape", sorted(SHAPES) + WOP_FORMAT_SHAPES)
 def test_residual_and_measured_spectrum(env, shape):
     """The largest rounding residual of the call stays under the certified bound evaluated at the measured
     max|G| of the call's own GGSWs, and that max|G| is what the general key conversion records for them."""

@@ -263,6 +263,83 @@ def test_table_shape_lists_are_complete():
     assert all(generic_class(s) is None for s in S.WOP_BSK)  # the WoP table's ring has a kernel of its own
 
 
+def test_table_sweeps_are_complete_and_collect_without_the_library():
+    """The GPU sweeps over the optimizer's tables (tests/test_gpu_table_sweep.py and the WoP cases of the circuit
+    bootstrap, vertical packing and bit extraction files): importing them, which is all that test collection does,
+    must not load libconcrete_hip.so (a GPU test imports torch first), and their parameter lists
+    are the lists of tests/table_shapes.py, less what NOT_SWEPT names with its evidence."""
+    import subprocess
+    mods = ["test_gpu_table_sweep", "test_gpu_circuit_bootstrap", "test_gpu_vertical_packing", "test_gpu_extract_bits",
+            "test_gpu_pbs_generic"]
+    code = ("import sys; sys.path[:0] = [%r, %r]\n"
+            "for m in %r: __import__(m)\n"
+            "from concrete_amd import _native\n"
+            "assert _native._lib is None, 'a GPU test module loads the native library at import time'\n"
+            "assert not [l for l in open('/proc/self/maps') if 'libconcrete_hip' in l]\n"
+            "print('collected clean')\n" % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                                             os.path.dirname(os.path.abspath(__file__)), mods))
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "collected clean" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+
+    import test_gpu_circuit_bootstrap as CB
+    import test_gpu_extract_bits as EB
+    import test_gpu_table_sweep as T
+    import test_gpu_vertical_packing as VP
+
+    def params(fn, name="case"):
+        return [m.args[1] for m in fn.pytestmark if m.name == "parametrize" and m.args[0] == name][0]
+
+    # PBS and keyswitch: swept + not swept = the table's list, and the not-swept span at most 2 dispatch classes
+    assert params(T.test_pbs_table_shape_bit_exact, "shape") == T.PBS_SWEPT
+    assert sorted(set(T.PBS_SWEPT) | set(T.NOT_SWEPT)) == S.PBS_SHAPES and len(S.PBS_SHAPES) == 99
+    assert not set(T.PBS_SWEPT) & set(T.NOT_SWEPT) and all(T.NOT_SWEPT.values())
+    L = _native.lib()
+
+    def dispatch_class(shape):
+        k, N, level, base_log = shape
+        limbs, bits = C.c_uint32(), C.c_uint32()
+        kind = L.concrete_hip_bsk_format(k, N, level, C.byref(limbs), C.byref(bits))
+        return kind, k, N, min((k + 1) * level, 9), limbs.value, -(-base_log // bits.value), level * base_log <= 31
+
+    assert len({dispatch_class(s) for s in T.NOT_SWEPT}) <= 2
+    assert T.NOT_SWEPT == {}  # the target
+    assert {T.pbs_steps(s[1]) for s in S.PBS_SHAPES} == {2, 3, 4}
+    assert all(T.pbs_width(s) == 3 for s in S.PBS_SHAPES if s not in S.V0_PBS)
+    assert all(1 <= T.pbs_width(s) <= 10 for s in S.PBS_SHAPES)
+    ks_cases = params(T.test_keyswitch_table_decomposition_bit_exact)
+    assert sorted({c[0] for c in ks_cases} | set(T.KS_NOT_SWEPT)) == S.KS_DECOMPS and len(S.KS_DECOMPS) == 29
+    assert T.KS_NOT_SWEPT == {} and all({(d, b) for b in (5, 67)} <= set(ks_cases) for d in T.KS_SWEPT)
+    # the VALU kernel's chunk forms over the table: 4 chunks at three decompositions, 3 at the rest, never the
+    # 64-bit products; every decomposition is exact on the matrix cores at the sweep's K = 200 l
+    assert [d for d in S.KS_DECOMPS if T.ks_valu_chunks(*d) == 4] == T.KS_FOUR_CHUNKS
+    assert {T.ks_valu_chunks(*d) for d in S.KS_DECOMPS} == {3, 4}
+    assert max(b for _, b in S.KS_DECOMPS) <= 5 and min(T.KS_BATCHES) < 64 <= max(T.KS_BATCHES)
+    # fp-ks: the table's seven decompositions on the small shapes and on the table's ring
+    assert set(S.WOP_PP) <= set(params(CB.test_fp_keyswitch_bit_exact, "decomp"))
+    assert params(CB.test_fp_keyswitch_at_the_table_ring, "decomp") == S.WOP_PP and len(S.WOP_PP) == 7
+    # circuit bootstrap: the 32 distinct (cb, pp) pairs on n512, those of at most 2 fp-ks levels on the ring
+    pairs = S.distinct(S.WOP_ROWS, "cb_l", "cb_b", "pp_l", "pp_b")
+    cb_cases = params(CB.test_circuit_bootstrap_table_pairs)
+    assert len(pairs) == 32 and sorted(q for s, q in cb_cases if s == "n512") == pairs
+    assert sorted(q for s, q in cb_cases if s == "k2n1024") == [q for q in pairs if q[2] <= 2]
+    assert CB.CBS_SHAPES["k2n1024"][0][:2] == S.WOP_RING
+    # vertical packing: the 20 GGSW decompositions at the table's ring, and one per key format for the residual
+    vp_cases = params(VP.test_bit_exact_against_the_reference)
+    assert sorted(VP.WOP_SHAPES[n] for n, g in vp_cases if n in VP.WOP_SHAPES and g == (3, 4, 3, 3)) == \
+        [S.WOP_RING + d for d in S.WOP_CB] and len(S.WOP_CB) == 20
+    from oracle import keyref
+    fmts = {keyref.generic_limb_bits(*VP.WOP_SHAPES[n][:3]) for n in VP.WOP_FORMAT_SHAPES}
+    assert len(fmts) == len(VP.WOP_FORMAT_SHAPES) == 7 and "wop_l1b14" in VP.WOP_FORMAT_SHAPES
+    assert set(VP.WOP_FORMAT_SHAPES) <= set(params(VP.test_residual_and_measured_spectrum, "shape"))
+    # bit extraction: three rows of the table, the extremes of its BSK levels and of its keyswitch levels
+    cols = ("bits", "log_norm2", "br_l", "br_b", "ks_l", "ks_b")
+    rows = {tuple(r[c] for c in cols) for r in S.WOP_ROWS}
+    assert set(EB.WOP_ROWS.values()) <= rows and set(EB.WOP_ROWS) <= set(params(EB.test_bit_exact_against_oracle, "name"))
+    assert EB.WOP_ROWS["wop_fewest_bsk_levels"][2] == min(r["br_l"] for r in S.WOP_ROWS) == 2
+    assert EB.WOP_ROWS["wop_most_bsk_levels"][2] == max(r["br_l"] for r in S.WOP_ROWS) == 45
+    assert EB.WOP_ROWS["wop_deepest_keyswitch"][4] == max(r["ks_l"] for r in S.WOP_ROWS) == 15
+
+
 def test_wop_table_coverage():
     """Every row of the optimizer's WoP-PBS table (tests/golden/wop_pbs_last_128_rows.json, from
     v0-parameters/ref/wop_pbs_last_128 by tests/golden/make_wop_rows.py) is accepted, with the row's own
