@@ -67,6 +67,20 @@ SIGNATURES = {
     "concrete_hip_circuit_bootstrap_scratch_bytes": (u64, [u32, u32, u32, u32, u32]),
     "concrete_hip_circuit_bootstrap_supported": (i32, [u32, u32, u32, u32, u32, u32, u32, u32]),
     "concrete_hip_fpksk_size_words": (u64, [u32, u32, u32]),
+    "scratch_cuda_circuit_bootstrap_vertical_packing_64": (None, [vp, u32, C.POINTER(vp), C.POINTER(u32)] + [u32] * 7 +
+                                                           [C.c_bool]),
+    "cuda_circuit_bootstrap_vertical_packing_64": (None, [vp, u32, vp, vp, vp, vp, vp, vp] + [u32] * 13),
+    "cleanup_cuda_circuit_bootstrap_vertical_packing": (None, [vp, u32, C.POINTER(vp)]),
+    "scratch_cuda_wop_pbs_64": (None, [vp, u32, C.POINTER(vp), C.POINTER(u32), C.POINTER(u32)] + [u32] * 9 +
+                                [C.c_bool]),
+    "cuda_wop_pbs_64": (None, [vp, u32, vp, vp, vp, vp, vp, vp, vp] + [u32] * 17),
+    "cleanup_cuda_wop_pbs": (None, [vp, u32, C.POINTER(vp)]),
+    "concrete_hip_circuit_bootstrap_vertical_packing": (i32, [vp, u32, vp, vp, vp, vp, vp] + [u32] * 12 +
+                                                        [vp, u64, C.POINTER(C.c_double)]),
+    "concrete_hip_wop_pbs_crt": (i32, [vp, u32, vp, vp, vp, vp, vp, vp, vp] + [u32] * 13 +
+                                 [vp, u64, C.POINTER(C.c_double)]),
+    "concrete_hip_wop_pbs_scratch_bytes": (u64, [u32] * 8),
+    "concrete_hip_wop_pbs_supported": (i32, [u32] * 11),
     "concrete_hip_abi_version": (u32, []),
     "concrete_hip_last_error": (C.c_char_p, []),
     "concrete_hip_pbs_supported": (i32, [u32, u32, u32, u32]),
@@ -107,7 +121,12 @@ SIGNATURES = {
     "concrete_hip_keyset_destroy": (None, [vp]),
     "concrete_hip_keyset_add_bsk": (i32, [vp, u32, vp, u32, u32, u32, u32, u32]),
     "concrete_hip_keyset_add_ksk": (i32, [vp, u32, vp, u32, u32, u32, u32]),
+    "concrete_hip_keyset_add_fpksk": (i32, [vp, u32, vp, u32, u32, u32, u32, u32]),
     "concrete_hip_keyset_set_devices": (i32, [vp, vp, u32]),
+    "memref_wop_pbs_crt_buffer_hip_u64": (None, [vp, vp] + [u64] * 5 + [vp, vp] + [u64] * 5 + [vp, vp] + [u64] * 5 +
+                                          [vp, vp] + [u64] * 3 + [u32] * 13 + [vp]),
+    "memref_wop_pbs_crt_buffer_cuda_u64": (None, [vp, vp] + [u64] * 5 + [vp, vp] + [u64] * 5 + [vp, vp] + [u64] * 5 +
+                                           [vp, vp] + [u64] * 3 + [u32] * 13 + [vp]),
     "memref_keyswitch_lwe_hip_u64": (None, [vp, vp, u64, u64, u64, vp, vp, u64, u64, u64, u32, u32, u32, u32, u32, vp]),
     "memref_bootstrap_lwe_hip_u64": (None, [vp, vp, u64, u64, u64, vp, vp, u64, u64, u64, vp, vp, u64, u64, u64,
                                             u32, u32, u32, u32, u32, u32, vp]),

@@ -489,3 +489,71 @@ def circuit_bootstrap(p: PbsParams, fbsk, fpksk_dev, lwe_in, delta_log: int, pks
         0 if scratch is None else scratch.numel() * scratch.element_size(), _ptr(pbs_out)),
         "concrete_hip_circuit_bootstrap")
     return out
+
+
+# ---------------------------------------------------------------------------------------
+# The WoP-PBS end to end: chained drivers (concrete_hip_wop_pbs_crt)
+# ---------------------------------------------------------------------------------------
+def wop_pbs_supported(p: PbsParams, pksk_level: int, pksk_base_log: int, cbs_level: int, cbs_base_log: int) -> bool:
+    """The conjunction of the three stages' _supported predicates for what the chain hands them."""
+    return bool(_native.lib().concrete_hip_wop_pbs_supported(p.n, p.k, p.N, p.level, p.base_log, p.ks_level,
+                                                            p.ks_base_log, pksk_level, pksk_base_log, cbs_level,
+                                                            cbs_base_log))
+
+
+def wop_pbs_scratch_bytes(p: PbsParams, cbs_level: int, num_blocks: int, number_of_bits: int, tau: int,
+                          batch: int = 1) -> int:
+    """Scratch bytes of a chained call: `batch` values of number_of_bits boolean inputs and tau LUTs, num_blocks
+    stage-1 inputs per value (0: circuit_bootstrap_vertical_packing, which has no stage 1)."""
+    return int(_native.lib().concrete_hip_wop_pbs_scratch_bytes(p.n, p.k, p.N, cbs_level, num_blocks, number_of_bits,
+                                                                tau, batch))
+
+
+def _scratch_args(scratch):
+    return _ptr(scratch), 0 if scratch is None else scratch.numel() * scratch.element_size()
+
+
+def circuit_bootstrap_vertical_packing(p: PbsParams, fbsk, fpksk_dev, bits, luts, pksk_level: int, pksk_base_log: int,
+                                       cbs_level: int, cbs_base_log: int, out=None, scratch=None):
+    """Stages 2 and 3 on device tensors: bits (lookups, t, n+1), the bit ciphertexts at 2^63, most significant
+    first; luts (tau, 2^t) cleartext words shared by the lookups -> ((lookups, tau, kN+1) int64, max|G|)."""
+    torch = _torch()
+    device = bits.device
+    lookups, t = bits.shape[0], bits.shape[1]
+    tau = luts.shape[0]
+    if bits.shape[2] != p.n + 1 or not bits.is_contiguous():
+        raise ValueError(f"bits: need a contiguous (lookups, t, {p.n + 1}) tensor, got {tuple(bits.shape)}")
+    if luts.shape[1] != 1 << t or not luts.is_contiguous():
+        raise ValueError(f"luts: need a contiguous ({tau}, {1 << t}) tensor, got {tuple(luts.shape)}")
+    if out is None:
+        out = torch.empty((lookups, tau, p.lwe_out_size), dtype=torch.int64, device=device)
+    max_g = C.c_double(0.0)
+    _native.check(_native.lib().concrete_hip_circuit_bootstrap_vertical_packing(
+        _stream(device), _gpu_index(device), _ptr(out), _ptr(bits), _ptr(luts), _ptr(fbsk), _ptr(fpksk_dev), p.n, p.k,
+        p.N, p.level, p.base_log, pksk_level, pksk_base_log, cbs_level, cbs_base_log, t, tau, lookups,
+        *_scratch_args(scratch), C.byref(max_g)), "concrete_hip_circuit_bootstrap_vertical_packing")
+    return out, max_g.value
+
+
+def wop_pbs_crt(p: PbsParams, fbsk, ksk_dev, fpksk_dev, blocks, luts, moduli, pksk_level: int, pksk_base_log: int,
+                cbs_level: int, cbs_base_log: int, out=None, scratch=None):
+    """The CRT WoP-PBS on device tensors: blocks (batch, len(moduli), kN+1), luts (len(moduli), 2^t) cleartext
+    words with t = sum crt_bits(m_i) -> ((batch, len(moduli), kN+1) int64, max|G|).  blocks is not modified."""
+    torch = _torch()
+    device = blocks.device
+    batch, nblk = blocks.shape[0], blocks.shape[1]
+    mods = np.ascontiguousarray(moduli, dtype=np.uint64)
+    t = sum(crt_bits(m) for m in moduli)
+    if nblk != len(mods) or blocks.shape[2] != p.big_n + 1 or not blocks.is_contiguous():
+        raise ValueError(f"blocks: need a contiguous (batch, {len(mods)}, {p.big_n + 1}) tensor, got {tuple(blocks.shape)}")
+    if tuple(luts.shape) != (nblk, 1 << t) or not luts.is_contiguous():
+        raise ValueError(f"luts: need a contiguous ({nblk}, {1 << t}) tensor, got {tuple(luts.shape)}")
+    if out is None:
+        out = torch.empty((batch, nblk, p.lwe_out_size), dtype=torch.int64, device=device)
+    max_g = C.c_double(0.0)
+    _native.check(_native.lib().concrete_hip_wop_pbs_crt(
+        _stream(device), _gpu_index(device), _ptr(out), _ptr(blocks), _ptr(luts), _ptr(fbsk), _ptr(ksk_dev),
+        _ptr(fpksk_dev), _ptr(mods), nblk, batch, p.n, p.k, p.N, p.level, p.base_log, p.ks_level, p.ks_base_log,
+        pksk_level, pksk_base_log, cbs_level, cbs_base_log, *_scratch_args(scratch), C.byref(max_g)),
+        "concrete_hip_wop_pbs_crt")
+    return out, max_g.value

@@ -30,6 +30,7 @@
 
 #include "common.hpp"
 #include "pbs.hpp"
+#include "circuit_bootstrap.hpp"
 #include "companion.hpp"
 #include "runtime.hpp"
 
@@ -80,6 +81,7 @@ void* g_resolver_user = nullptr;
 
 BskEntry* keyset_bsk_entry(concrete_hip_keyset* ks, uint32_t idx) { return entry(ks->bsk, idx, ks->m, false); }
 KskEntry* keyset_ksk_entry(concrete_hip_keyset* ks, uint32_t idx) { return entry(ks->ksk, idx, ks->m, false); }
+FpkskEntry* keyset_fpksk_entry(concrete_hip_keyset* ks, uint32_t idx) { return entry(ks->fpksk, idx, ks->m, false); }
 
 void* keyset_bsk_on(concrete_hip_keyset* ks, uint32_t idx, uint32_t gpu, hipStream_t s) {
   BskEntry* e = keyset_bsk_entry(ks, idx);
@@ -125,6 +127,23 @@ void* keyset_ksk_on(concrete_hip_keyset* ks, uint32_t idx, uint32_t gpu, hipStre
   CHIP_CHECK(hipMemcpyAsync(d, e->host.data(), bytes, hipMemcpyHostToDevice, s));
   CHIP_CHECK(hipStreamSynchronize(s));
   track_device_buffer(d);  // resident for the keyset's lifetime: its int8 key bytes may be cached
+  e->dev[gpu] = d;
+  return d;
+}
+
+void* keyset_fpksk_on(concrete_hip_keyset* ks, uint32_t idx, uint32_t gpu, hipStream_t s) {
+  FpkskEntry* e = keyset_fpksk_entry(ks, idx);
+  if (!e) rt_die("packing keyswitch key index %u not registered", idx);
+  RT_ASSERT(gpu < RT_MAX_DEV);
+  if (e->dev[gpu]) return e->dev[gpu];
+  std::lock_guard<std::mutex> g(e->m);
+  if (e->dev[gpu]) return e->dev[gpu];
+  CHIP_CHECK(hipSetDevice((int)gpu));
+  void* d = nullptr;
+  const uint64_t bytes = e->host.size() * 8ull;
+  CHIP_CHECK(hipMalloc(&d, bytes));
+  CHIP_CHECK(hipMemcpyAsync(d, e->host.data(), bytes, hipMemcpyHostToDevice, s));
+  CHIP_CHECK(hipStreamSynchronize(s));
   e->dev[gpu] = d;
   return d;
 }
@@ -409,6 +428,78 @@ void free_keys(concrete_hip_keyset* ks) {
       }
     delete e;
   }
+  for (FpkskEntry* e : ks->fpksk) {
+    if (!e) continue;
+    for (int d = 0; d < RT_MAX_DEV; ++d)
+      if (e->dev[d]) {
+        CHIP_CHECK(hipSetDevice(d));
+        CHIP_CHECK(hipFree(e->dev[d]));
+      }
+    delete e;
+  }
+}
+
+// The CRT WoP-PBS of one value on the keyset's first device: one slice slot (its stream, staging and grow-only
+// buffers: input blocks, output blocks, cleartext LUTs, the call's scratch), one concrete_hip_wop_pbs_crt.
+struct WopCrtCall {
+  const uint64_t* in;
+  uint64_t* out;
+  uint64_t out_stride0;
+  const uint64_t* lut;
+  uint64_t lut_stride0, lut_words;
+  const uint64_t* moduli;
+  uint32_t blocks, n, k, N, cbs_level, cbs_base_log, ksk_level, ksk_base_log, bsk_level, bsk_base_log, pksk_level,
+      pksk_base_log, ksk_index, bsk_index, pksk_index;
+};
+
+void run_wop_crt(concrete_hip_keyset* ks, const WopCrtCall& c) {
+  {
+    // the registered keys must have the call's parameters: their sizes and layouts follow them
+    BskEntry* b = keyset_bsk_entry(ks, c.bsk_index);
+    if (!b) rt_die("bootstrap key index %u not registered", c.bsk_index);
+    RT_ASSERT(b->n == c.n && b->k == c.k && b->N == c.N && b->level == c.bsk_level && b->base_log == c.bsk_base_log);
+    KskEntry* e = keyset_ksk_entry(ks, c.ksk_index);
+    if (!e) rt_die("keyswitch key index %u not registered", c.ksk_index);
+    RT_ASSERT(e->level == c.ksk_level && e->base_log == c.ksk_base_log && e->n_in == (uint64_t)c.k * c.N &&
+              e->n_out == c.n);
+    FpkskEntry* f = keyset_fpksk_entry(ks, c.pksk_index);
+    if (!f) rt_die("packing keyswitch key index %u not registered", c.pksk_index);
+    RT_ASSERT(f->level == c.pksk_level && f->base_log == c.pksk_base_log && f->k == c.k && f->N == c.N);
+  }
+  uint32_t t = 0;
+  for (uint32_t i = 0; i < c.blocks; ++i) t += c.moduli[i] < 2 ? 0 : 64u - (uint32_t)__builtin_clzll(c.moduli[i] - 1);
+  const uint64_t W = (uint64_t)c.k * c.N + 1;
+  const uint64_t need = concrete_hip_wop_pbs_scratch_bytes(c.n, c.k, c.N, c.cbs_level, c.blocks, t, c.blocks, 1);
+  if (need == 0) rt_die("wop_pbs_crt: %u blocks, %u bits: no scratch size for these parameters", c.blocks, t);
+  run_sliced(ks, 1, [&](SliceSlot& sl, uint64_t, uint64_t) {
+    CHIP_CHECK(hipSetDevice((int)sl.gpu));
+    void* fbsk = keyset_bsk_on(ks, c.bsk_index, sl.gpu, sl.s);
+    void* dk = keyset_ksk_on(ks, c.ksk_index, sl.gpu, sl.s);
+    void* dp = keyset_fpksk_on(ks, c.pksk_index, sl.gpu, sl.s);
+    uint64_t* d_in = slot_buf(sl, 0, c.blocks * W * 8);
+    uint64_t* d_out = slot_buf(sl, 1, c.blocks * W * 8);
+    uint64_t* d_lut = slot_buf(sl, 2, c.blocks * c.lut_words * 8);
+    uint64_t* d_scratch = slot_buf(sl, 3, need);
+    mark(ks, sl, 0);
+    sl.stage_in.resize(c.blocks * W);
+    copy_rows(sl.stage_in.data(), W, c.in, W, c.blocks, W);
+    CHIP_CHECK(copy_h2d(d_in, sl.stage_in, sl.stage_in.data(), c.blocks * W * 8, sl.s));
+    sl.stage_lut.resize(c.blocks * c.lut_words);
+    copy_rows(sl.stage_lut.data(), c.lut_words, c.lut, c.lut_stride0, c.blocks, c.lut_words);
+    CHIP_CHECK(copy_h2d(d_lut, sl.stage_lut, sl.stage_lut.data(), c.blocks * c.lut_words * 8, sl.s));
+    mark(ks, sl, 1);
+    if (concrete_hip_wop_pbs_crt(sl.s, sl.gpu, d_out, d_in, d_lut, fbsk, (const uint64_t*)dk, (const uint64_t*)dp,
+                                 c.moduli, c.blocks, 1, c.n, c.k, c.N, c.bsk_level, c.bsk_base_log, c.ksk_level,
+                                 c.ksk_base_log, c.pksk_level, c.pksk_base_log, c.cbs_level, c.cbs_base_log, d_scratch,
+                                 need, nullptr) != 0)
+      rt_die("%s", concrete_hip_last_error());
+    mark(ks, sl, 2);
+    sl.stage_out.resize(c.blocks * W);
+    CHIP_CHECK(copy_d2h(sl.stage_out.data(), sl.stage_out, d_out, c.blocks * W * 8, sl.s));
+    mark(ks, sl, 3);
+    CHIP_CHECK(hipStreamSynchronize(sl.s));
+    copy_rows(c.out, c.out_stride0, sl.stage_out.data(), W, c.blocks, W);
+  });
 }
 
 }  // namespace
@@ -493,6 +584,30 @@ int concrete_hip_keyset_add_ksk(concrete_hip_keyset* ks, uint32_t ksk_index, con
   const uint64_t len = (uint64_t)input_lwe_dim * level * ((uint64_t)output_lwe_dim + 1);
   e->host.assign(ksk, ksk + len);
   e->level = level, e->base_log = base_log, e->n_in = input_lwe_dim, e->n_out = output_lwe_dim;
+  return 0;
+}
+
+int concrete_hip_keyset_add_fpksk(concrete_hip_keyset* ks, uint32_t pksk_index, const uint64_t* fpksk, uint32_t level,
+                                  uint32_t base_log, uint32_t input_lwe_dim, uint32_t glwe_dim, uint32_t poly_size) {
+  const uint64_t len = concrete_hip_fpksk_size_words(glwe_dim, poly_size, level);
+  if (!ks || !fpksk || glwe_dim == 0 || (uint64_t)glwe_dim * poly_size != input_lwe_dim || len == 0 || len >> 58) {
+    set_error("keyset_add_fpksk: bad argument");
+    return -3;
+  }
+  if (!fpks_params_ok(glwe_dim, poly_size, level, base_log)) {  // the circuit bootstrap's own predicate
+    set_error("keyset_add_fpksk: unsupported parameters level=%u base_log=%u k=%u N=%u", level, base_log, glwe_dim,
+              poly_size);
+    return -2;
+  }
+  FpkskEntry* e = entry(ks->fpksk, pksk_index, ks->m, true);
+  std::lock_guard<std::mutex> g(e->m);
+  for (int d = 0; d < RT_MAX_DEV; ++d)
+    if (e->dev[d]) {
+      set_error("keyset_add_fpksk: index %u already resident", pksk_index);
+      return -3;
+    }
+  e->host.assign(fpksk, fpksk + len);
+  e->level = level, e->base_log = base_log, e->k = glwe_dim, e->N = poly_size;
   return 0;
 }
 
@@ -657,6 +772,45 @@ void memref_keyswitch_lwe_hip_u64(uint64_t* out_allocated, uint64_t* out_aligned
                                        base_log, input_lwe_dim, output_lwe_dim, ksk_index, context);
 }
 
+void memref_wop_pbs_crt_buffer_hip_u64(
+    uint64_t* out_allocated, uint64_t* out_aligned, uint64_t out_offset, uint64_t out_size_0, uint64_t out_size_1,
+    uint64_t out_stride_0, uint64_t out_stride_1, uint64_t* in_allocated, uint64_t* in_aligned, uint64_t in_offset,
+    uint64_t in_size_0, uint64_t in_size_1, uint64_t in_stride_0, uint64_t in_stride_1, uint64_t* lut_ct_allocated,
+    uint64_t* lut_ct_aligned, uint64_t lut_ct_offset, uint64_t lut_ct_size0, uint64_t lut_ct_size1,
+    uint64_t lut_ct_stride0, uint64_t lut_ct_stride1, uint64_t* crt_decomp_allocated, uint64_t* crt_decomp_aligned,
+    uint64_t crt_decomp_offset, uint64_t crt_decomp_size, uint64_t crt_decomp_stride, uint32_t lwe_small_dim,
+    uint32_t cbs_level_count, uint32_t cbs_base_log, uint32_t ksk_level_count, uint32_t ksk_base_log,
+    uint32_t bsk_level_count, uint32_t bsk_base_log, uint32_t fpksk_level_count, uint32_t fpksk_base_log,
+    uint32_t polynomial_size, uint32_t ksk_index, uint32_t bsk_index, uint32_t pksk_index,
+    concrete_hip_keyset* context) {
+  (void)out_allocated, (void)in_allocated, (void)lut_ct_allocated, (void)crt_decomp_allocated;
+  // wrappers.cpp:886-901
+  RT_ASSERT(out_stride_1 == 1 && out_stride_0 >= out_size_1);
+  RT_ASSERT(in_stride_1 == 1 && in_stride_0 == in_size_1);
+  RT_ASSERT(out_size_0 == in_size_0 && out_size_0 == crt_decomp_size);
+  RT_ASSERT(out_size_1 == in_size_1);
+  RT_ASSERT(polynomial_size > 0 && in_size_1 > 1 && (in_size_1 - 1) % polynomial_size == 0);
+  RT_ASSERT(in_size_1 - 1 <= 0xffffffffull && crt_decomp_size >= 1 && crt_decomp_size <= 16);
+  RT_ASSERT(context);
+  // the moduli, gathered: the total number of bits fixes the LUT's size (wrappers.cpp:967-973)
+  uint64_t moduli[16];
+  uint64_t t = 0;
+  for (uint64_t i = 0; i < crt_decomp_size; ++i) {
+    moduli[i] = crt_decomp_aligned[crt_decomp_offset + i * crt_decomp_stride];
+    RT_ASSERT(moduli[i] >= 2 && moduli[i] <= (1ull << 63));
+    t += 64u - (uint32_t)__builtin_clzll(moduli[i] - 1);
+  }
+  RT_ASSERT(t < 48);
+  RT_ASSERT(lut_ct_size0 == out_size_0 && lut_ct_size1 == (1ull << t));
+  RT_ASSERT(lut_ct_stride1 == 1 && lut_ct_stride0 >= lut_ct_size1);
+  run_wop_crt(context,
+              WopCrtCall{in_aligned + in_offset, out_aligned + out_offset, out_stride_0, lut_ct_aligned + lut_ct_offset,
+                         lut_ct_stride0, lut_ct_size1, moduli, (uint32_t)crt_decomp_size, lwe_small_dim,
+                         (uint32_t)((in_size_1 - 1) / polynomial_size), polynomial_size, cbs_level_count, cbs_base_log,
+                         ksk_level_count, ksk_base_log, bsk_level_count, bsk_base_log, fpksk_level_count,
+                         fpksk_base_log, ksk_index, bsk_index, pksk_index});
+}
+
 // ------------------------------------------------------------------------------------------
 // memref_*_cuda_u64: the reference's names (wrappers.h:246-300); the last argument is the
 // caller's runtime context, resolved to its keyset
@@ -725,6 +879,25 @@ void memref_batched_mapped_bootstrap_lwe_cuda_u64(
       ct0_aligned, ct0_offset, ct0_size0, ct0_size1, ct0_stride0, ct0_stride1, tlu_allocated, tlu_aligned, tlu_offset,
       tlu_size0, tlu_size1, tlu_stride0, tlu_stride1, input_lwe_dim, poly_size, level, base_log, glwe_dim, bsk_index,
       keyset_of_context(context));
+}
+
+void memref_wop_pbs_crt_buffer_cuda_u64(
+    uint64_t* out_allocated, uint64_t* out_aligned, uint64_t out_offset, uint64_t out_size_0, uint64_t out_size_1,
+    uint64_t out_stride_0, uint64_t out_stride_1, uint64_t* in_allocated, uint64_t* in_aligned, uint64_t in_offset,
+    uint64_t in_size_0, uint64_t in_size_1, uint64_t in_stride_0, uint64_t in_stride_1, uint64_t* lut_ct_allocated,
+    uint64_t* lut_ct_aligned, uint64_t lut_ct_offset, uint64_t lut_ct_size0, uint64_t lut_ct_size1,
+    uint64_t lut_ct_stride0, uint64_t lut_ct_stride1, uint64_t* crt_decomp_allocated, uint64_t* crt_decomp_aligned,
+    uint64_t crt_decomp_offset, uint64_t crt_decomp_size, uint64_t crt_decomp_stride, uint32_t lwe_small_dim,
+    uint32_t cbs_level_count, uint32_t cbs_base_log, uint32_t ksk_level_count, uint32_t ksk_base_log,
+    uint32_t bsk_level_count, uint32_t bsk_base_log, uint32_t fpksk_level_count, uint32_t fpksk_base_log,
+    uint32_t polynomial_size, uint32_t ksk_index, uint32_t bsk_index, uint32_t pksk_index, void* context) {
+  memref_wop_pbs_crt_buffer_hip_u64(
+      out_allocated, out_aligned, out_offset, out_size_0, out_size_1, out_stride_0, out_stride_1, in_allocated,
+      in_aligned, in_offset, in_size_0, in_size_1, in_stride_0, in_stride_1, lut_ct_allocated, lut_ct_aligned,
+      lut_ct_offset, lut_ct_size0, lut_ct_size1, lut_ct_stride0, lut_ct_stride1, crt_decomp_allocated,
+      crt_decomp_aligned, crt_decomp_offset, crt_decomp_size, crt_decomp_stride, lwe_small_dim, cbs_level_count,
+      cbs_base_log, ksk_level_count, ksk_base_log, bsk_level_count, bsk_base_log, fpksk_level_count, fpksk_base_log,
+      polynomial_size, ksk_index, bsk_index, pksk_index, keyset_of_context(context));
 }
 
 }  // extern "C"

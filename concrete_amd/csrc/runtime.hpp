@@ -38,6 +38,13 @@ struct KskEntry {
   void* dev[RT_MAX_DEV] = {};
   std::mutex m;
 };
+// the k + 1 packing keyswitch keys of a circuit bootstrap: [k+1][kN+1][level][(k+1)N] (circuit_bootstrap.hip)
+struct FpkskEntry {
+  std::vector<uint64_t> host;
+  uint32_t level = 0, base_log = 0, k = 0, N = 0;
+  void* dev[RT_MAX_DEV] = {};
+  std::mutex m;
+};
 
 // Host memory the devices copy from and to: grow-only page-locked memory (hipHostMalloc), so H2D /
 // D2H copies are DMA at link speed and asynchronous (pageable copies are staged by the runtime in
@@ -164,6 +171,7 @@ struct concrete_hip_keyset {
   std::mutex m;
   std::vector<chip::BskEntry*> bsk;  // indexed by bsk_index
   std::vector<chip::KskEntry*> ksk;
+  std::vector<chip::FpkskEntry*> fpksk;  // indexed by pksk_index
   std::vector<uint32_t> devices{0};
   // call_m guards the pool and the timing state; it is held only to take or return a slot set
   std::mutex call_m;
@@ -180,7 +188,10 @@ namespace chip {
 void* keyset_bsk_on(concrete_hip_keyset* ks, uint32_t idx, uint32_t gpu, hipStream_t s);
 // device copy of the standard KSK on `gpu`, uploaded on first use
 void* keyset_ksk_on(concrete_hip_keyset* ks, uint32_t idx, uint32_t gpu, hipStream_t s);
+// device copy of the fp-ks key list on `gpu`, uploaded on first use
+void* keyset_fpksk_on(concrete_hip_keyset* ks, uint32_t idx, uint32_t gpu, hipStream_t s);
 BskEntry* keyset_bsk_entry(concrete_hip_keyset* ks, uint32_t idx);
+FpkskEntry* keyset_fpksk_entry(concrete_hip_keyset* ks, uint32_t idx);
 KskEntry* keyset_ksk_entry(concrete_hip_keyset* ks, uint32_t idx);
 // keyset bound to a runtime context pointer (concrete_hip_context_bind / resolver); aborts if none
 concrete_hip_keyset* keyset_of_context(const void* ctx);

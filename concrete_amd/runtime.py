@@ -41,6 +41,13 @@ class Keyset:
         _native.check(self.lib.concrete_hip_keyset_add_ksk(self.h, index, ksk.ctypes.data, p.ks_level,
                                                            p.ks_base_log, p.big_n, p.n), "keyset_add_ksk")
 
+    def add_fpksk(self, index, fpksk, p, level, base_log):
+        """The k + 1 packing keyswitch keys of a circuit bootstrap, (k+1, kN+1, level, (k+1)N) words."""
+        fpksk = np.ascontiguousarray(fpksk, dtype=np.uint64)
+        assert fpksk.size == (p.k + 1) * (p.big_n + 1) * level * (p.k + 1) * p.N
+        _native.check(self.lib.concrete_hip_keyset_add_fpksk(self.h, index, fpksk.ctypes.data, level, base_log,
+                                                             p.big_n, p.k, p.N), "keyset_add_fpksk")
+
     def set_timing(self, on=True):
         """Record HIP events around every slice of the following calls (concrete_hip_keyset_set_timing)."""
         self.lib.concrete_hip_keyset_set_timing(self.h, int(on))
@@ -169,6 +176,34 @@ def keyswitch_cuda(context: int, p, ct: np.ndarray, ksk_index=0) -> np.ndarray:
     L.memref_keyswitch_lwe_cuda_u64(*_desc(out), *_desc(ct), p.ks_level, p.ks_base_log, p.big_n, p.n, ksk_index,
                                     context)
     return out
+
+
+def _desc_at(a: np.ndarray, offset: int):
+    """Descriptor of `a` as a view that starts `offset` words into an allocation of its own."""
+    flat = np.zeros(offset + a.size, dtype=np.uint64)
+    flat[offset:] = a.reshape(-1)
+    p = flat.ctypes.data
+    tail = [a.shape[0], 1] if a.ndim == 1 else [a.shape[0], a.shape[1], a.shape[1], 1]
+    return flat, [p, p, offset] + tail
+
+
+def wop_pbs_crt(ks_or_context, p, blocks: np.ndarray, luts: np.ndarray, moduli, pksk, cbs, offset: int = 0,
+                ksk_index=0, bsk_index=0, pksk_index=0, cuda_name: bool = False) -> np.ndarray:
+    """memref_wop_pbs_crt_buffer_hip_u64 (a Keyset) or, with cuda_name, memref_wop_pbs_crt_buffer_cuda_u64 (a
+    runtime-context pointer): the CRT WoP-PBS of one value.  blocks (nblk, kN+1), luts (nblk, 2^t) cleartext,
+    moduli (nblk,); pksk and cbs are (level, base_log).  Every memref starts `offset` words into its allocation."""
+    L = _native.lib()
+    blocks = np.ascontiguousarray(blocks, dtype=np.uint64)
+    luts = np.ascontiguousarray(luts, dtype=np.uint64)
+    mods = np.ascontiguousarray(moduli, dtype=np.uint64)
+    out_flat, d_out = _desc_at(np.zeros_like(blocks), offset)
+    _in, d_in = _desc_at(blocks, offset)
+    _lut, d_lut = _desc_at(luts, offset)
+    _mod, d_mod = _desc_at(mods, offset)
+    f = L.memref_wop_pbs_crt_buffer_cuda_u64 if cuda_name else L.memref_wop_pbs_crt_buffer_hip_u64
+    f(*d_out, *d_in, *d_lut, *d_mod, p.n, cbs[0], cbs[1], p.ks_level, p.ks_base_log, p.level, p.base_log, pksk[0],
+      pksk[1], p.N, ksk_index, bsk_index, pksk_index, ks_or_context if cuda_name else ks_or_context.h)
+    return out_flat[offset:].reshape(blocks.shape).copy()
 
 
 # ------------------------------------------------------------------------------------------

@@ -191,6 +191,58 @@ void cuda_circuit_bootstrap_64(void *stream, uint32_t gpu_index, void *ggsw_out,
                                uint32_t base_log_cbs, uint32_t number_of_samples, uint32_t max_shared_memory);
 void cleanup_cuda_circuit_bootstrap(void *stream, uint32_t gpu_index, int8_t **cbs_buffer);
 
+/* The WoP-PBS drivers (concrete-cuda rust_api/src/cuda_bind.rs:650-813): stages 2 and 3, and
+ * all three stages, in one call.  The reference's implementation is not part of the sources this backend was
+ * written against; this is the reading of its argument lists:
+ * cuda_circuit_bootstrap_vertical_packing_64: lwe_array_in holds number_of_inputs bit ciphertexts (lwe_dimension
+ * + 1 words each, the bit at cbs_delta_log), most significant first; they are circuit-bootstrapped (lut indexes
+ * (sample, v) -> v) and select, by vertical packing at (level_count_cbs, base_log_cbs) with r = max(t - log2 N, 0)
+ * tree bits and min(t, log2 N) rotation bits (t = number_of_inputs), one entry of each of the lut_number LUTs;
+ * lut_vector is [lut_number][max(2^t, N)] device words (a LUT of fewer than N words sits at the front of a zero
+ * polynomial); lwe_array_out receives lut_number rows of kN + 1 words.
+ * cuda_wop_pbs_64: from each of the number_of_inputs inputs (kN + 1 words) number_of_bits_to_extract bits are
+ * extracted at delta_log, input 0 supplying the most significant ones; ONE lookup follows with t =
+ * number_of_inputs * number_of_bits_to_extract and number_of_inputs LUTs in the layout above; lwe_array_out
+ * receives number_of_inputs rows of kN + 1 words.  At most 16 inputs.  cbs_delta_log must be 63, where the
+ * extraction leaves its bits.
+ * The scratch calls write *cbs_delta_log = 63 and *delta_log = 64 - number_of_bits_of_message_including_padding.
+ * max_shared_memory is accepted and ignored.  A scratch call with allocate_gpu_memory = false leaves NULL, and a
+ * NULL buffer makes the call take stream-ordered pool scratch.  fourier_bsk is as in cuda_extract_bits_64.  One
+ * host synchronisation of the stream per call in the steady state (vertical packing's gate; see
+ * concrete_hip_wop_pbs_crt).  Bad arguments, unsupported parameters
+ * and keys or GGSWs that fail an exactness gate abort. */
+void scratch_cuda_circuit_bootstrap_vertical_packing_64(void *stream, uint32_t gpu_index, int8_t **cbs_vp_buffer,
+                                                        uint32_t *cbs_delta_log, uint32_t glwe_dimension,
+                                                        uint32_t lwe_dimension, uint32_t polynomial_size,
+                                                        uint32_t level_count_cbs, uint32_t number_of_inputs,
+                                                        uint32_t lut_number, uint32_t max_shared_memory,
+                                                        bool allocate_gpu_memory);
+void cuda_circuit_bootstrap_vertical_packing_64(void *stream, uint32_t gpu_index, void *lwe_array_out,
+                                                const void *lwe_array_in, const void *fourier_bsk,
+                                                const void *cbs_fpksk, const void *lut_vector, int8_t *cbs_vp_buffer,
+                                                uint32_t cbs_delta_log, uint32_t polynomial_size,
+                                                uint32_t glwe_dimension, uint32_t lwe_dimension,
+                                                uint32_t level_count_bsk, uint32_t base_log_bsk,
+                                                uint32_t level_count_pksk, uint32_t base_log_pksk,
+                                                uint32_t level_count_cbs, uint32_t base_log_cbs,
+                                                uint32_t number_of_inputs, uint32_t lut_number,
+                                                uint32_t max_shared_memory);
+void cleanup_cuda_circuit_bootstrap_vertical_packing(void *stream, uint32_t gpu_index, int8_t **cbs_vp_buffer);
+void scratch_cuda_wop_pbs_64(void *stream, uint32_t gpu_index, int8_t **wop_pbs_buffer, uint32_t *delta_log,
+                             uint32_t *cbs_delta_log, uint32_t glwe_dimension, uint32_t lwe_dimension,
+                             uint32_t polynomial_size, uint32_t level_count_cbs, uint32_t level_count_bsk,
+                             uint32_t number_of_bits_of_message_including_padding, uint32_t number_of_bits_to_extract,
+                             uint32_t number_of_inputs, uint32_t max_shared_memory, bool allocate_gpu_memory);
+void cuda_wop_pbs_64(void *stream, uint32_t gpu_index, void *lwe_array_out, const void *lwe_array_in,
+                     const void *lut_vector, const void *fourier_bsk, const void *ksk, const void *cbs_fpksk,
+                     int8_t *wop_pbs_buffer, uint32_t cbs_delta_log, uint32_t glwe_dimension, uint32_t lwe_dimension,
+                     uint32_t polynomial_size, uint32_t base_log_bsk, uint32_t level_count_bsk, uint32_t base_log_ksk,
+                     uint32_t level_count_ksk, uint32_t base_log_pksk, uint32_t level_count_pksk, uint32_t base_log_cbs,
+                     uint32_t level_count_cbs, uint32_t number_of_bits_of_message_including_padding,
+                     uint32_t number_of_bits_to_extract, uint32_t delta_log, uint32_t number_of_inputs,
+                     uint32_t max_shared_memory);
+void cleanup_cuda_wop_pbs(void *stream, uint32_t gpu_index, int8_t **wop_pbs_buffer);
+
 /* ------------------------------------------------------------------------------------------
  * Part 2: extensions (return 0 on success, < 0 on error; message via concrete_hip_last_error)
  * ------------------------------------------------------------------------------------------ */
@@ -207,7 +259,9 @@ void cleanup_cuda_circuit_bootstrap(void *stream, uint32_t gpu_index, int8_t **c
  * The same holds for vertical packing (cuda_cmux_tree_64, cuda_blind_rotate_and_sample_extraction_64,
  * concrete_hip_vertical_packing*): concrete_hip_vertical_packing_supported; and for the circuit bootstrap
  * (cuda_circuit_bootstrap_64, cuda_fp_keyswitch_lwe_to_glwe_64, concrete_hip_circuit_bootstrap*,
- * concrete_hip_fp_keyswitch): concrete_hip_circuit_bootstrap_supported. */
+ * concrete_hip_fp_keyswitch): concrete_hip_circuit_bootstrap_supported; and for the chained WoP-PBS
+ * (cuda_circuit_bootstrap_vertical_packing_64, cuda_wop_pbs_64, concrete_hip_wop_pbs*,
+ * concrete_hip_circuit_bootstrap_vertical_packing, memref_wop_pbs_crt_buffer_*): concrete_hip_wop_pbs_supported. */
 uint32_t concrete_hip_abi_version(void);
 /* thread-local message of the last failed concrete_hip_* call */
 const char *concrete_hip_last_error(void);
@@ -402,6 +456,64 @@ int concrete_hip_circuit_bootstrap_supported(uint32_t glwe_dimension, uint32_t p
                                              uint32_t level_cbs, uint32_t base_log_cbs);
 /* u64 words of the list of k + 1 fp-ks keys: (k+1) (kN+1) level (k+1)N; 0 when that overflows 64 bits */
 uint64_t concrete_hip_fpksk_size_words(uint32_t glwe_dimension, uint32_t polynomial_size, uint32_t level_count);
+/* The WoP-PBS end to end, with a status code.  One lookup with t boolean inputs and tau LUTs of
+ * 2^t words: r = max(t - log2 N, 0), m = min(t, log2 N); concrete_hip_circuit_bootstrap over the t bit ciphertexts
+ * at delta_log 63, whose output is the ggsw_in of concrete_hip_vertical_packing at (level_cbs, base_log_cbs), r,
+ * mbr_size = m, tau.  The LUT operand [tau][2^r][N] is the cleartext array [tau][2^t] as it stands when
+ * t >= log2 N (the caller's pointer is passed through); for t < log2 N the 2^t words go to the front of a zero
+ * polynomial (concrete-cpu's Ordering::Less branch).
+ * concrete_hip_circuit_bootstrap_vertical_packing: stages 2 and 3 for num_lookups lookups that share the LUTs.
+ *   lwe_array_in   [num_lookups][number_of_inputs][lwe_dimension + 1], the bits at 2^63, most significant first
+ *   lwe_array_out  [num_lookups][tau][kN+1]
+ * concrete_hip_wop_pbs_crt: the CRT front of the runtime's memref_wop_pbs_crt_buffer (compiler lib/Runtime/
+ * wrappers.cpp:903-965), stage 1, then the call above with num_lookups = batch.  Block i of modulus moduli[i]
+ * (HOST array of num_blocks entries, each 2 .. 2^63) yields nb_i = ceil(log2 m_i) bits at delta_log 64 - nb_i
+ * after 2^(63-nb_i) - 2^(59-nb_i) is taken off its body (the second term dropped when nb_i > 59); per value the
+ * bits are ordered [block num_blocks-1 | ... | block 0], each most significant first; t = sum nb_i, tau =
+ * num_blocks.  Stage 1 is a single concrete_hip_extract_bits over batch * num_blocks rows.
+ *   lwe_array_in   [batch][num_blocks][kN+1], not modified
+ *   cleartext_luts [num_blocks][2^t]
+ *   lwe_array_out  [batch][num_blocks][kN+1]
+ * Every other pointer is device memory too; fourier_bsk as in concrete_hip_pbs, ksk as in concrete_hip_keyswitch,
+ * fp_ksk as in concrete_hip_circuit_bootstrap.  scratch: 16-byte aligned, at least
+ * concrete_hip_wop_pbs_scratch_bytes() bytes, or NULL for stream-ordered pool scratch (one allocation); every
+ * intermediate buffer is carved from it.  ggsw_spectrum_max: as concrete_hip_vertical_packing.  In the steady
+ * state the whole call makes ONE host synchronisation of the stream, vertical packing's for its gate, and the
+ * driver adds none.  What the stages may add, as in their own calls: the first PBS on a key that needs its
+ * general-format companion builds it and synchronises once (concrete_hip_pbs), and bit extraction waits for the
+ * calling thread's previous upload of index data, normally long done, before it reuses the staging block.
+ * Checked before the first device call: -1 null pointer; -3 number_of_inputs == 0, tau == 0, num_blocks == 0 or
+ * above 16, a modulus out of range, t > log2 N + 24, sizes that overflow, a scratch buffer too small or
+ * misaligned; -2 parameters for which concrete_hip_wop_pbs_supported (for the first call: its last two
+ * conditions) is 0.  A key or GGSWs that fail an exactness gate: -2.  A refused call leaves lwe_array_out
+ * untouched. */
+int concrete_hip_circuit_bootstrap_vertical_packing(
+    void *stream, uint32_t gpu_index, uint64_t *lwe_array_out, const uint64_t *lwe_array_in,
+    const uint64_t *cleartext_luts, const void *fourier_bsk, const uint64_t *fp_ksk, uint32_t lwe_dimension,
+    uint32_t glwe_dimension, uint32_t polynomial_size, uint32_t level_bsk, uint32_t base_log_bsk, uint32_t level_pksk,
+    uint32_t base_log_pksk, uint32_t level_cbs, uint32_t base_log_cbs, uint32_t number_of_inputs, uint32_t tau,
+    uint32_t num_lookups, void *scratch, uint64_t scratch_bytes, double *ggsw_spectrum_max);
+int concrete_hip_wop_pbs_crt(void *stream, uint32_t gpu_index, uint64_t *lwe_array_out, const uint64_t *lwe_array_in,
+                             const uint64_t *cleartext_luts, const void *fourier_bsk, const uint64_t *ksk,
+                             const uint64_t *fp_ksk, const uint64_t *moduli, uint32_t num_blocks, uint32_t batch,
+                             uint32_t lwe_dimension, uint32_t glwe_dimension, uint32_t polynomial_size,
+                             uint32_t level_bsk, uint32_t base_log_bsk, uint32_t level_ksk, uint32_t base_log_ksk,
+                             uint32_t level_pksk, uint32_t base_log_pksk, uint32_t level_cbs, uint32_t base_log_cbs,
+                             void *scratch, uint64_t scratch_bytes, double *ggsw_spectrum_max);
+/* scratch bytes of a chained call on `batch` values (lookups) of number_of_bits = t boolean inputs and tau LUTs;
+ * num_blocks: the stage-1 inputs per value (CRT blocks), 0 for concrete_hip_circuit_bootstrap_vertical_packing.
+ * 0 for t == 0, tau == 0, batch == 0, level_cbs == 0, num_blocks > t, t > log2 N + 24, a shape a stage has no
+ * scratch size for, or sizes that overflow.  Does not decrease with batch, t, tau or level_cbs. */
+uint64_t concrete_hip_wop_pbs_scratch_bytes(uint32_t lwe_dimension, uint32_t glwe_dimension, uint32_t polynomial_size,
+                                            uint32_t level_cbs, uint32_t num_blocks, uint32_t number_of_bits,
+                                            uint32_t tau, uint32_t batch);
+/* 1 exactly when concrete_hip_extract_bits_supported(kN, lwe_dimension, k, N, base_log_bsk, level_bsk, base_log_ksk,
+ * level_ksk), concrete_hip_circuit_bootstrap_supported(k, N, level_bsk, base_log_bsk, level_pksk, base_log_pksk,
+ * level_cbs, base_log_cbs) and concrete_hip_vertical_packing_supported(k, N, level_cbs, base_log_cbs) all hold */
+int concrete_hip_wop_pbs_supported(uint32_t lwe_dimension, uint32_t glwe_dimension, uint32_t polynomial_size,
+                                   uint32_t level_bsk, uint32_t base_log_bsk, uint32_t level_ksk, uint32_t base_log_ksk,
+                                   uint32_t level_pksk, uint32_t base_log_pksk, uint32_t level_cbs,
+                                   uint32_t base_log_cbs);
 /* Fourier key registered for a `dest` of cuda_convert_lwe_programmable_bootstrap_key_64, or NULL */
 const void *concrete_hip_lookup_bsk(const void *bootstrapping_key);
 /* Release what the backend derived from device buffer `ptr` (a registered Fourier key whose `dest`
@@ -503,6 +615,13 @@ int concrete_hip_keyset_add_bsk(concrete_hip_keyset *ks, uint32_t bsk_index, con
                                 uint32_t glwe_dim, uint32_t level, uint32_t base_log, uint32_t poly_size);
 int concrete_hip_keyset_add_ksk(concrete_hip_keyset *ks, uint32_t ksk_index, const uint64_t *ksk, uint32_t level,
                                 uint32_t base_log, uint32_t input_lwe_dim, uint32_t output_lwe_dim);
+/* The list of k + 1 packing keyswitch (fp-ks) keys of a circuit bootstrap, under the index the runtime context
+ * uses (context.h fp_keyswitch_key_buffer(pksk_index)): a host buffer of concrete_hip_fpksk_size_words(glwe_dim,
+ * poly_size, level) words in the layout given with cuda_fp_keyswitch_lwe_to_glwe_64, copied; the key is uploaded
+ * on first use, stays resident per device like a KSK, and is freed with the keyset.  input_lwe_dim must be
+ * glwe_dim * poly_size.  -3 bad argument, -2 a (level, base_log) the fp-ks does not take. */
+int concrete_hip_keyset_add_fpksk(concrete_hip_keyset *ks, uint32_t pksk_index, const uint64_t *fpksk, uint32_t level,
+                                  uint32_t base_log, uint32_t input_lwe_dim, uint32_t glwe_dim, uint32_t poly_size);
 /* devices the batched calls shard across (default: device 0); entries may repeat.  Every slice of
  * a call runs on its own host thread, stream and cached device buffers. */
 int concrete_hip_keyset_set_devices(concrete_hip_keyset *ks, const uint32_t *devices, uint32_t count);
@@ -559,6 +678,22 @@ void memref_batched_mapped_bootstrap_lwe_hip_u64(
     uint64_t *tlu_aligned, uint64_t tlu_offset, uint64_t tlu_size0, uint64_t tlu_size1, uint64_t tlu_stride0,
     uint64_t tlu_stride1, uint32_t input_lwe_dim, uint32_t poly_size, uint32_t level, uint32_t base_log,
     uint32_t glwe_dim, uint32_t bsk_index, concrete_hip_keyset *context);
+/* The CRT WoP-PBS of one value (compiler lib/Runtime/wrappers.cpp:855-997, memref_wop_pbs_crt_buffer: the same
+ * argument list and shape assertions): out and in are (blocks, kN+1) host memrefs, lut_ct (blocks, 2^t) cleartext
+ * LUTs with t = sum ceil(log2 m_i), crt_decomp the blocks' moduli.  One concrete_hip_wop_pbs_crt call with
+ * batch = 1 on the keyset's first device (a WoP call is not sharded), with the keyset's resident BSK, KSK and
+ * fp-ks keys, whose registered parameters must be the call's. */
+void memref_wop_pbs_crt_buffer_hip_u64(
+    uint64_t *out_allocated, uint64_t *out_aligned, uint64_t out_offset, uint64_t out_size_0, uint64_t out_size_1,
+    uint64_t out_stride_0, uint64_t out_stride_1, uint64_t *in_allocated, uint64_t *in_aligned, uint64_t in_offset,
+    uint64_t in_size_0, uint64_t in_size_1, uint64_t in_stride_0, uint64_t in_stride_1, uint64_t *lut_ct_allocated,
+    uint64_t *lut_ct_aligned, uint64_t lut_ct_offset, uint64_t lut_ct_size0, uint64_t lut_ct_size1,
+    uint64_t lut_ct_stride0, uint64_t lut_ct_stride1, uint64_t *crt_decomp_allocated, uint64_t *crt_decomp_aligned,
+    uint64_t crt_decomp_offset, uint64_t crt_decomp_size, uint64_t crt_decomp_stride, uint32_t lwe_small_dim,
+    uint32_t cbs_level_count, uint32_t cbs_base_log, uint32_t ksk_level_count, uint32_t ksk_base_log,
+    uint32_t bsk_level_count, uint32_t bsk_base_log, uint32_t fpksk_level_count, uint32_t fpksk_base_log,
+    uint32_t polynomial_size, uint32_t ksk_index, uint32_t bsk_index, uint32_t pksk_index,
+    concrete_hip_keyset *context);
 
 /* The direct GPU route under the reference's own names and argument lists
  * (compiler include/concretelang/Runtime/wrappers.h:246-300, lib/Runtime/wrappers.cpp:70-363):
@@ -599,6 +734,18 @@ void memref_batched_mapped_bootstrap_lwe_cuda_u64(
     uint64_t *tlu_aligned, uint64_t tlu_offset, uint64_t tlu_size0, uint64_t tlu_size1, uint64_t tlu_stride0,
     uint64_t tlu_stride1, uint32_t input_lwe_dim, uint32_t poly_size, uint32_t level, uint32_t base_log,
     uint32_t glwe_dim, uint32_t bsk_index, void *context);
+/* memref_wop_pbs_crt_buffer with the context resolved as above.  The reference has no GPU variant of this
+ * wrapper: the compiler's CAPI lowering has to emit this name for the op. */
+void memref_wop_pbs_crt_buffer_cuda_u64(
+    uint64_t *out_allocated, uint64_t *out_aligned, uint64_t out_offset, uint64_t out_size_0, uint64_t out_size_1,
+    uint64_t out_stride_0, uint64_t out_stride_1, uint64_t *in_allocated, uint64_t *in_aligned, uint64_t in_offset,
+    uint64_t in_size_0, uint64_t in_size_1, uint64_t in_stride_0, uint64_t in_stride_1, uint64_t *lut_ct_allocated,
+    uint64_t *lut_ct_aligned, uint64_t lut_ct_offset, uint64_t lut_ct_size0, uint64_t lut_ct_size1,
+    uint64_t lut_ct_stride0, uint64_t lut_ct_stride1, uint64_t *crt_decomp_allocated, uint64_t *crt_decomp_aligned,
+    uint64_t crt_decomp_offset, uint64_t crt_decomp_size, uint64_t crt_decomp_stride, uint32_t lwe_small_dim,
+    uint32_t cbs_level_count, uint32_t cbs_base_log, uint32_t ksk_level_count, uint32_t ksk_base_log,
+    uint32_t bsk_level_count, uint32_t bsk_base_log, uint32_t fpksk_level_count, uint32_t fpksk_base_log,
+    uint32_t polynomial_size, uint32_t ksk_index, uint32_t bsk_index, uint32_t pksk_index, void *context);
 
 /* ------------------------------------------------------------------------------------------
  * Part 5: the SDFG stream emulator — the default GPU route of a circuit compiled with SDFG
