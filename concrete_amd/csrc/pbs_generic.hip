@@ -216,10 +216,14 @@ struct SubDigit {
         bmask(split_ ? ((St)1 << bits) - (St)1 : ~(St)0),
         sb((int)bits),
         split(split_) {}
+  // last: the digit's top sub-digit is whatever is left, not balanced again: when base_log is a multiple of
+  // b, a digit in [B/2 - 2^(b-1), B/2] leaves +2^(b-1), which the window [-2^(b-1), 2^(b-1)) would wrap to
+  // -2^(b-1) and so change the digit by B (zero half and an all-ones mask, as for one sub-digit)
   template <class V>  // V = Dg, or St for an unsigned value (the key converters)
-  __device__ __forceinline__ Dg take(V& D) const {
+  __device__ __forceinline__ Dg take(V& D, bool last = false) const {
     if (BRANCH && !split) return (Dg)D;
-    const Dg s = (Dg)(((St)D + half) & bmask) - (Dg)half;
+    const St h = last ? (St)0 : half, mk = last ? ~(St)0 : bmask;
+    const Dg s = (Dg)(((St)D + h) & mk) - (Dg)h;
     D = (D - (V)s) >> sb;
     return s;
   }
@@ -660,7 +664,7 @@ __global__ void __launch_bounds__(Geo<M>::BLOCK) gen_step_kernel(StepArgs a) {
         cplx* dst = Xc + ((uint64_t)q * a.subs + t) * M;
 #pragma unroll
         for (int e = 0; e < VPT; ++e) {
-          const int64_t s0 = sub.take(D[e]), s1 = sub.take(D[e + VPT]);
+          const int64_t s0 = sub.take(D[e], t + 1 == a.subs), s1 = sub.take(D[e + VPT], t + 1 == a.subs);
           const int j = tid + e * TH;
           const cplx z = cmul(cplx{(double)s0, (double)s1}, zeta(j));
           if constexpr (STAGE) {
@@ -928,7 +932,7 @@ __global__ void __launch_bounds__(Big<M>::NT) gen_big_step_kernel(StepArgs a) {
           cplx v[8];
 #pragma unroll
           for (int e = 0; e < 8; ++e) {
-            const Dg s0 = sub.take(D[sr][e]), s1 = sub.take(D[sr][e + 8]);
+            const Dg s0 = sub.take(D[sr][e], t + 1 == a.subs), s1 = sub.take(D[sr][e + 8], t + 1 == a.subs);
             v[e] = {(double)s0, (double)s1};
           }
 #ifndef DG_NOROW
@@ -1132,7 +1136,7 @@ __global__ void __launch_bounds__(512) gen_split_front_kernel(SplitArgs a) {
         cplx v[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-          const Dg s0 = sub.take(D[sr][e]), s1 = sub.take(D[sr][e + 8]);
+          const Dg s0 = sub.take(D[sr][e], t + 1 == a.subs), s1 = sub.take(D[sr][e + 8], t + 1 == a.subs);
           v[e] = {(double)s0, (double)s1};
         }
         fft512_fwd(v, xch, q.T, lane);
@@ -1621,7 +1625,7 @@ __global__ void __launch_bounds__(512) gen_fused_kernel(FusedArgs a) {
         cplx v[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-          const Dg s0 = sub.take(D[e]), s1 = sub.take(D[e + 8]);
+          const Dg s0 = sub.take(D[e], t + 1 == T), s1 = sub.take(D[e + 8], t + 1 == T);
           v[e] = {(double)s0, (double)s1};
         }
         fft512_fwd(v, row, TB, lane);
@@ -1903,7 +1907,7 @@ __global__ void __launch_bounds__(512) gen_coop_kernel(CoopArgs a) {
         cplx v[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-          const Dg s0 = sub.take(D[e]), s1 = sub.take(D[e + 8]);
+          const Dg s0 = sub.take(D[e], t + 1 == T), s1 = sub.take(D[e + 8], t + 1 == T);
           v[e] = {(double)s0, (double)s1};
         }
         fft512_fwd(v, row, TB, lane);
@@ -2365,7 +2369,7 @@ __global__ void __launch_bounds__((TileGeo<M, K1, KL, T, L, C>::NT)) gen_tile_ke
         cplx* xs = Xs + ((lct * KL + c * LV + q) * T + t) * M;
 #pragma unroll
         for (int e = 0; e < VPT; ++e) {
-          const int64_t s0 = sub.take(D[e]), s1 = sub.take(D[e + VPT]);
+          const int64_t s0 = sub.take(D[e], t + 1 == T), s1 = sub.take(D[e + VPT], t + 1 == T);
           const int j = tid + e * TH;
           xs[sw(j)] = cmul(cplx{(double)s0, (double)s1}, zeta(j));
         }
@@ -2724,7 +2728,7 @@ __global__ void __launch_bounds__(M / CMUX_VPT) gen_cmux_kernel(CmuxKernelArgs a
       for (uint32_t t = 0; t < a.subs; ++t) {
 #pragma unroll
         for (int e = 0; e < VPT; ++e) {
-          const int64_t s0 = sub.take(D[e]), s1 = sub.take(D[e + VPT]);
+          const int64_t s0 = sub.take(D[e], t + 1 == a.subs), s1 = sub.take(D[e + VPT], t + 1 == a.subs);
           const int j = tid + e * TH;
           buf[sw(j)] = cmul(cplx{(double)s0, (double)s1}, Zl[j]);
         }

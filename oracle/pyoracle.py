@@ -281,6 +281,14 @@ def keyswitch_batch(p: Params, lwe_in, ksk, nthreads=0):
     return out
 
 
+def decompose(x, l: int, logB: int) -> list:
+    """Closest-representative signed digits of the u64 word x (ora_decompose), least significant
+    level first: x rounded to l logB bits is sum_q digits[q] 2^(64 - (l - q) logB) mod 2^64."""
+    d = (C.c_int64 * l)()
+    lib().ora_decompose(C.c_uint64(int(x) & 0xFFFFFFFFFFFFFFFF), l, logB, d)
+    return [int(v) for v in d]
+
+
 def encode(m, width):
     return np.uint64(lib().ora_encode_native(int(m), width))
 

@@ -270,7 +270,7 @@ def test_table_sweeps_are_complete_and_collect_without_the_library():
     are the lists of tests/table_shapes.py, less what NOT_SWEPT names with its evidence."""
     import subprocess
     mods = ["test_gpu_table_sweep", "test_gpu_circuit_bootstrap", "test_gpu_vertical_packing", "test_gpu_extract_bits",
-            "test_gpu_pbs_generic"]
+            "test_gpu_pbs_generic", "test_gpu_worst_case"]
     code = ("import sys; sys.path[:0] = [%r, %r]\n"
             "for m in %r: __import__(m)\n"
             "from concrete_amd import _native\n"
