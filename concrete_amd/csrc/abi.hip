@@ -43,6 +43,26 @@ void keep_pool_memory() {
   done.fetch_or(bit, std::memory_order_acq_rel);
 }
 
+// Test hook: with CONCRETE_HIP_SCRATCH_FILL set, every scratch allocation of the library is filled
+// with that byte on the stream that will use it, so that a kernel reading a scratch word before any
+// kernel wrote it computes on the fill rather than on whatever the pool block last held
+// (tests/test_gpu_poisoned_scratch.py).  Read per call, as the other knobs tests change between calls;
+// unset or empty: nothing is issued.
+void scratch_fill(void* p, size_t bytes, hipStream_t s) {
+  const char* v = getenv("CONCRETE_HIP_SCRATCH_FILL");
+  if (!v || !*v || !p || !bytes) return;
+  CHIP_CHECK(hipMemsetAsync(p, (int)(strtoul(v, nullptr, 0) & 0xff), bytes, s));
+}
+
+// The library's one stream-ordered allocation: pool memory that stays mapped (above), filled under the
+// test hook.  Returns the allocation's status (the keyswitch falls back on a refusal).
+hipError_t pool_alloc(void** p, size_t bytes, hipStream_t s) {
+  keep_pool_memory();
+  const hipError_t e = hipMallocAsync(p, bytes, s);
+  if (e == hipSuccess) scratch_fill(*p, bytes, s);
+  return e;
+}
+
 static thread_local char g_err[512] = "";
 void set_error(const char* fmt, ...) {
   va_list ap;
@@ -281,10 +301,9 @@ static int convert_and_record(hipStream_t s, void* dest, const void* src, bool s
   const KeyFormat f = general ? generic_key_format(k, N, level) : key_format(k, N, level);
   const uint64_t* src_dev = (const uint64_t*)src;
   void* tmp = nullptr;
-  keep_pool_memory();
   if (!src_is_device) {
     const uint64_t bytes = std_bsk_bytes(n, k, level, N);
-    CHIP_CHECK(hipMallocAsync(&tmp, bytes, s));
+    CHIP_CHECK(pool_alloc(&tmp, bytes, s));
     CHIP_CHECK(hipMemcpyAsync(tmp, src, bytes, hipMemcpyHostToDevice, s));
     src_dev = (const uint64_t*)tmp;
   }
@@ -300,9 +319,8 @@ static int convert_and_record(hipStream_t s, void* dest, const void* src, bool s
 // ---- scratch handed out by scratch_cuda_* calls, and a call's own (companion.hpp) --------
 int8_t* ScratchRegistry::allocate(uint32_t gpu, uint64_t bytes, void* stream) {
   CHIP_CHECK(hipSetDevice((int)gpu));
-  keep_pool_memory();
   void* p = nullptr;
-  CHIP_CHECK(hipMallocAsync(&p, bytes, (hipStream_t)stream));
+  CHIP_CHECK(pool_alloc(&p, bytes, (hipStream_t)stream));
   std::lock_guard<std::mutex> g(mu_);
   bytes_[p] = bytes;
   return (int8_t*)p;
@@ -481,8 +499,7 @@ void* cuda_malloc_async(uint64_t size, void* stream, uint32_t gpu_index) {
   set_device(gpu_index);
   void* p = nullptr;
   if (size == 0) return nullptr;
-  keep_pool_memory();
-  CHIP_CHECK(hipMallocAsync(&p, size, (hipStream_t)stream));
+  CHIP_CHECK(pool_alloc(&p, size, (hipStream_t)stream));
   track_device_buffer(p);
   return p;
 }
@@ -803,9 +820,8 @@ void scratch_cuda_programmable_bootstrap_64(void* stream, uint32_t gpu_index, in
     return;
   }
   set_device(gpu_index);
-  keep_pool_memory();
   void* p = nullptr;
-  CHIP_CHECK(hipMallocAsync(&p, 256, (hipStream_t)stream));
+  CHIP_CHECK(pool_alloc(&p, 256, (hipStream_t)stream));
   CHIP_CHECK(hipMemsetAsync(p, 0, 256, (hipStream_t)stream));
   *pbs_buffer = (int8_t*)p;
 }

@@ -328,7 +328,7 @@ static void make_sroots(std::vector<ddc>& sr) {
 // A host table in stream-ordered device memory (freed by the caller after the launch).
 static ddc* upload_table(const std::vector<ddc>& t, hipStream_t s) {
   ddc* d = nullptr;
-  CHIP_CHECK(hipMallocAsync((void**)&d, t.size() * sizeof(ddc), s));
+  CHIP_CHECK(pool_alloc((void**)&d, t.size() * sizeof(ddc), s));
   CHIP_CHECK(hipMemcpyAsync(d, t.data(), t.size() * sizeof(ddc), hipMemcpyHostToDevice, s));
   return d;
 }
@@ -342,7 +342,6 @@ int convert_bsk_launch(const ConvertArgs& a) {
   }
   std::vector<ddc> zeta, tw, sr;
   make_tables(f.kind == KeyKind::SMALL ? a.N : 1024, zeta, tw);  // the others transform N = 1024 negacyclic polynomials
-  keep_pool_memory();
   ddc *dz = upload_table(zeta, a.stream), *dt = upload_table(tw, a.stream), *ds = nullptr;
   int rc;
   switch (f.kind) {

@@ -77,6 +77,12 @@ void key_spectrum_forget(const void* key);
 // before every stream-ordered allocation.
 void keep_pool_memory();
 
+// abi.hip: the library's stream-ordered allocation (keep_pool_memory, hipMallocAsync, scratch_fill); the
+// allocation's status.  scratch_fill: a no-op unless the test hook CONCRETE_HIP_SCRATCH_FILL names a
+// byte, then the block is set to it on s before the call's kernels run.
+hipError_t pool_alloc(void** p, size_t bytes, hipStream_t s);
+void scratch_fill(void* p, size_t bytes, hipStream_t s);
+
 // abi.hip: the cuda_* entry points' failure, as the reference's: the message on stderr, then abort.
 [[noreturn]] void die(const char* what);
 
@@ -116,8 +122,7 @@ struct CallScratch {
   char* base;
   CallScratch(void* callers, uint64_t bytes, hipStream_t s) : base((char*)callers), s_(s), owned_(!callers) {
     if (!owned_) return;
-    keep_pool_memory();
-    CHIP_CHECK(hipMallocAsync((void**)&base, bytes, s_));
+    CHIP_CHECK(pool_alloc((void**)&base, bytes, s_));
   }
   ~CallScratch() {  // on every return path; a failed CHIP_CHECK does not return at all (hip_fatal aborts)
     if (owned_) CHIP_CHECK(hipFreeAsync(base, s_));

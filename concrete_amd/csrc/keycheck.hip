@@ -103,8 +103,7 @@ double certified_bound(KeyKind kind, uint32_t k, uint32_t N, uint32_t level, uin
 // A zeroed sink for the conversion kernels' max |G|^2 (keycheck.hpp), stream-ordered.
 unsigned long long* key_spectrum_sink(hipStream_t s) {
   unsigned long long* d = nullptr;
-  keep_pool_memory();
-  CHIP_CHECK(hipMallocAsync((void**)&d, SPEC_SINK_WORDS * sizeof(unsigned long long), s));
+  CHIP_CHECK(pool_alloc((void**)&d, SPEC_SINK_WORDS * sizeof(unsigned long long), s));
   CHIP_CHECK(hipMemsetAsync(d, 0, SPEC_SINK_WORDS * sizeof(unsigned long long), s));
   return d;
 }

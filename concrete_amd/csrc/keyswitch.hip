@@ -398,7 +398,6 @@ static bool key_cache_on() {
 static int8_t* key_bytes(const KsArgs& a, uint32_t K, uint32_t W, uint32_t NP, uint32_t Ks, bool& owned) {
   int dev = 0;
   CHIP_CHECK(hipGetDevice(&dev));
-  keep_pool_memory();
   // A tracked key holds g_kb_mu from the tracked check to the insert, so a release_key_bytes of
   // the buffer on another thread falls before all of it or after all of it; any other key drops
   // the lock at once.
@@ -418,10 +417,11 @@ static int8_t* key_bytes(const KsArgs& a, uint32_t K, uint32_t W, uint32_t NP, u
   }
   int8_t* bt = nullptr;
   const size_t bytes = (size_t)8 * NP * Ks;
-  if ((cache ? hipMalloc((void**)&bt, bytes) : hipMallocAsync((void**)&bt, bytes, a.stream)) != hipSuccess) {
+  if ((cache ? hipMalloc((void**)&bt, bytes) : pool_alloc((void**)&bt, bytes, a.stream)) != hipSuccess) {
     (void)hipGetLastError();
     return nullptr;
   }
+  if (cache) scratch_fill(bt, bytes, a.stream);
   hipLaunchKernelGGL(ks_chunks_i8_kernel, dim3((NP + 255) / 256, Ks / 16), dim3(256), 0, a.stream, bt, a.ksk, K, W,
                      NP, Ks);
   owned = !cache;
@@ -517,14 +517,13 @@ static int keyswitch_mfma_launch(const KsArgs& a) {
   const uint32_t Ks = (kb + 7) * KSL_KB;
   CHIP_CHECK(hipFuncSetAttribute((const void*)ks_mfma_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                  (int)KSL_LDS));
-  keep_pool_memory();
   // test hook: refuse operand scratch above this many bytes (the VALU fallback then runs)
   if (const char* lim = getenv("CONCRETE_HIP_KS_SCRATCH_LIMIT"))
     if ((uint64_t)chunk * Ks + 8ull * NP * Ks > strtoull(lim, nullptr, 10)) return -5;
   bool bt_owned = false;
   int8_t* Bt = key_bytes(a, K, W, NP, Ks, bt_owned);
   int8_t* A = nullptr;
-  if (!Bt || hipMallocAsync((void**)&A, (size_t)chunk * Ks, a.stream) != hipSuccess) {
+  if (!Bt || pool_alloc((void**)&A, (size_t)chunk * Ks, a.stream) != hipSuccess) {
     // not enough device memory for the matrix-core operands: the scratch-free VALU kernel
     (void)hipGetLastError();
     if (Bt && bt_owned) CHIP_CHECK(hipFreeAsync(Bt, a.stream));

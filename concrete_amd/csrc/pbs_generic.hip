@@ -57,11 +57,6 @@
 
 namespace chip {
 
-// abi.hip: raise the device's default memory-pool release threshold once, so stream-ordered
-// scratch freed by one call stays pooled for the next (each keyswitch call at cfg2 otherwise paid
-// ~0.1 ms of allocation).
-void keep_pool_memory();
-
 // ------------------------------------------------------------------------------------------
 // key format and exactness gate (host)
 // ------------------------------------------------------------------------------------------
@@ -2989,8 +2984,7 @@ static bool coop_dispatch(const PbsArgs& a, const Tables& tb, uint32_t T, uint32
       (uint32_t)std::min<uint64_t>(a.num_samples, std::min<uint64_t>(env_knob("CONCRETE_HIP_GEN_CHUNK", 4096), 8192));
   const uint64_t flag_bytes = ((2ull * chunk + 1) * 4 + 15) / 16 * 16;
   char* scratch = nullptr;
-  keep_pool_memory();
-  CHIP_CHECK(hipMallocAsync((void**)&scratch, flag_bytes + (xb_ct + yb_ct) * chunk, a.stream));
+  CHIP_CHECK(pool_alloc((void**)&scratch, flag_bytes + (xb_ct + yb_ct) * chunk, a.stream));
   uint32_t* flags = reinterpret_cast<uint32_t*>(scratch);
   cplx* xb = reinterpret_cast<cplx*>(scratch + flag_bytes);
   cplx* yb = reinterpret_cast<cplx*>(scratch + flag_bytes + xb_ct * chunk);
@@ -3048,8 +3042,7 @@ static int run_chunks(const PbsArgs& a, const char* what, uint32_t L, uint32_t T
   hipStream_t st[MAX_NS];
   for (int q = 0; q < NS; ++q) st[q] = q == 0 ? a.stream : side_stream(q);
   void* scratch = nullptr;
-  keep_pool_memory();
-  CHIP_CHECK(hipMallocAsync(&scratch, per_ct * chunk * NS, a.stream));
+  CHIP_CHECK(pool_alloc(&scratch, per_ct * chunk * NS, a.stream));
   hipEvent_t fork = nullptr;
   if (NS > 1) {  // the library streams start after the caller's prior work and the allocation
     CHIP_CHECK(hipEventCreateWithFlags(&fork, hipEventDisableTiming));
@@ -3164,8 +3157,7 @@ static int convert_split_launch(const ConvertArgs& a, const KeyFormat& fmt, cons
   const uint64_t per_poly = (uint64_t)fmt.limbs * G::M * sizeof(cplx);
   const uint32_t batch = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(polys, (1ull << 30) / per_poly));
   void* scratch = nullptr;
-  keep_pool_memory();
-  CHIP_CHECK(hipMallocAsync(&scratch, per_poly * batch, a.stream));
+  CHIP_CHECK(pool_alloc(&scratch, per_poly * batch, a.stream));
   for (uint64_t p0 = 0; p0 < polys; p0 += batch) {
     const uint32_t nb = (uint32_t)std::min<uint64_t>(batch, polys - p0);
     SplitConvArgs c{reinterpret_cast<cplx*>(scratch), a.src_dev, tb.Tau, tb.WR, reinterpret_cast<cplx*>(a.dest), p0,

@@ -228,6 +228,7 @@ uint64_t* slot_buf(SliceSlot& sl, int i, uint64_t bytes) {
     CHIP_CHECK(hipMalloc(&sl.buf[i], bytes));
     sl.cap[i] = bytes;
   }
+  scratch_fill(sl.buf[i], bytes, sl.s);  // test hook: a reused buffer is poisoned like a new one
   return (uint64_t*)sl.buf[i];
 }
 

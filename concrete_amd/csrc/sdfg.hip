@@ -38,6 +38,7 @@
 #include <unordered_set>
 
 #include "common.hpp"
+#include "companion.hpp"
 #include "pbs.hpp"
 #include "runtime.hpp"
 
@@ -367,6 +368,7 @@ void run_chunk(const Plan& P, Slot& sl, uint64_t start, uint64_t cnt) {
       CHIP_CHECK(hipMalloc(&sl.buf[nbuf], bytes));
       sl.cap[nbuf] = bytes;
     }
+    scratch_fill(sl.buf[nbuf], bytes, s);  // test hook: a reused buffer is poisoned like a new one
     return (uint64_t*)sl.buf[nbuf++];
   };
   // inputs: this chunk's rows (or the whole broadcast operand)

@@ -27,7 +27,9 @@ def _run(env, fn, *arrays, n, count, extra_in=None):
     return B.to_host(out)
 
 
-@pytest.mark.parametrize("n,count", [(630, 1), (630, 37), (2048, 300), (1, 5)])
+# (4095, 2049): 8,392,704 words, one row past the 256 * 64 * 256 * 2 a single pass of linear_kernel's grid covers
+# (the grid-stride loop's second pass); (2, 3): an odd total of 9, the last thread's second word is past the end
+@pytest.mark.parametrize("n,count", [(630, 1), (630, 37), (2048, 300), (1, 5), (4095, 2049), (2, 3)])
 def test_linear_ops_exact(env, n, count):
     rng = np.random.default_rng(n + count)
     a = rng.integers(0, 2 ** 64, size=(count, n + 1), dtype=np.uint64)

@@ -188,6 +188,28 @@ def test_pmc_records_not_attached_under_dispatch_overrides(monkeypatch):
     assert bench.dispatched_kernel(1280, "cfg2", 256) is None or bench.pmc_f64_flop(1280, "cfg2")[0] is None
 
 
+def test_stream_ordered_allocations_go_through_pool_alloc():
+    """Every stream-ordered allocation of the library is pool_alloc's (abi.hip): the pool stays mapped and the
+    test hook CONCRETE_HIP_SCRATCH_FILL poisons the block (tests/test_gpu_poisoned_scratch.py).  A new site that
+    calls hipMallocAsync itself would be scratch no test poisons."""
+    import glob
+    import re
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "concrete_amd", "csrc")
+    sites = []
+    for path in sorted(glob.glob(os.path.join(csrc, "*"))):
+        if not os.path.isfile(path):
+            continue
+        with open(path, encoding="utf-8", errors="replace") as fh:
+            text = fh.read()
+        text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+        text = re.sub(r"//[^\n]*", " ", text)
+        for m in re.finditer(r"hipMallocAsync\s*\(", text):
+            # the enclosing function: the last definition at column 0 before the call
+            heads = re.findall(r"^[A-Za-z_][^\n;{}]*?\b(\w+)\s*\([^;{}]*\)\s*(?:const\s*)?\{", text[:m.start()], flags=re.M)
+            sites.append((os.path.basename(path), heads[-1] if heads else None))
+    assert sites == [("abi.hip", "pool_alloc")], sites
+
+
 def test_optimizer_table_coverage():
     """Every row of the optimizer's reference table (tests/golden/v0_last_128_rows.json, from
     v0-parameters/ref/v0_last_128 by tests/golden/make_v0_rows.py) from 1 to 8 bits, at every log
